@@ -10,9 +10,12 @@ windows, LOCAL alignment with traceback, default vg scoring 1/4/6/1/5.
 Multi-GPU: ONE read stream of reads-per-GPU x N reads is cut into contiguous shards
 (vg_amd/shard.py, pairs kept together), one process per GPU, no data-path collective
 -> weak scaling.  torch is used only for process-group plumbing (barrier, max-reduce
-of the times).  Besides the resident-kernel rate (`value`) every rank also streams its
+of the times).  A plain run sets up, warms up, times --steps steps and prints the line.
+With --full, besides the resident-kernel rate (`value`) every rank also streams its
 shard from host buffers (pack + kernels + fetch), with the host's packing threads
-divided among the ranks; the slowest rank sets `end_to_end_*_per_s`.
+divided among the ranks; the slowest rank sets `end_to_end_*_per_s`; rank 0 of a
+one-GPU run adds the CPU baseline, the parity check and the `secondary` records.
+--dump-outputs DIR writes a sample of the last timed step's results as .npy files.
 
 Prints ONE JSON line on rank 0.
 """
@@ -92,6 +95,32 @@ PMC_BYTES_PER_UNIT, PMC_SOURCE = _pmc_constants()
 
 def traffic_source(workload):
     return "stored constant from the rocprofv3 PMC passes %s (not measured in this run), scaled by the units of one launch" % PMC_SOURCE[workload]
+
+
+DUMP_SAMPLE = 32768       # problems in --dump-outputs' sample: at most 48 ops each, 11 float64 arrays -> under 40 MB in all
+
+
+def dump_gssw_outputs(out_dir, res, ops):
+    """--dump-outputs: what a caller of the timed path receives from its last step (vgk_gssw_fetch: one result row per problem and the
+    CIGAR ops), for a fixed sample of the problems (seed 2026, sorted) so that two builds can be compared output for output.  Every field
+    goes out as float64 (exact for these 32-bit integers); the sampled problems' ops are concatenated in sample order, `n_ops` cuts them
+    (ops_begin, a storage offset, is left out)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(res)
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(2026).choice(n, DUMP_SAMPLE, replace=False))
+    sample = res[idx]
+    arrays = {"read_index": idx}
+    for f in ("score", "status", "end_node", "end_offset", "end_read", "first_offset", "n_ops"):
+        arrays[f] = sample[f]
+    beg = sample["ops_begin"].astype(np.int64)
+    nop = sample["n_ops"].astype(np.int64)
+    nop = np.where(beg + nop <= len(ops), nop, 0)            # (a row whose ops are not in the fetched array contributes none)
+    first = np.repeat(beg - (np.cumsum(nop) - nop), nop)       # ops index = position in the concatenation + (begin - its start there)
+    picked = ops[np.arange(int(nop.sum())) + first]
+    arrays.update(op_node=picked["node"], op_len=picked["len"], op_code=picked["op"])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 
@@ -1486,9 +1515,19 @@ def main():
                          "giraffe-style pinned X-drop tail alignments on a variation graph; banded = configs[4] stand-in: "
                          "banded global alignments between chained anchors; gapless = giraffe's first stage: "
                          "haplotype-consistent gapless extension of seeds; wfa = the long-read chaining stage's WFA connects and tails")
+    ap.add_argument("--full", action="store_true", help="linear / tails workloads: besides the timed steps, run every other leg — the two-lane steady state, the CPU baseline "
+                         "and the parity check against the oracle, the end-to-end legs from host buffers and (linear, one GPU) the `secondary` records, written to "
+                         "bench_secondary.json; --no-cpu, --no-e2e and --no-secondary leave single legs out.  Without it a run sets up, warms up, times the steps "
+                         "and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="linear / tails workloads: after the timed steps write what the last step computed "
+                         "to DIR/<name>.npy (float64; rank 0's shard): the result fields and the CIGAR ops of a fixed, seeded sample of at most %d problems" % DUMP_SAMPLE)
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and not (args.workload == "linear" or (args.workload == "tails" and args.tails_per_problem_graphs)):
+        raise SystemExit("bench.py: --dump-outputs covers the linear workload (and --workload tails --tails-per-problem-graphs) only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:          # no launcher around this process: become one
         raise SystemExit(relaunch_on_ranks(args.gpus))
 
@@ -1625,7 +1664,7 @@ def main():
     # traceback of one batch — bound by memory latency — runs under the fill of the next — bound by VALU issue.  Two batches are
     # resident (the same reads packed twice); step i runs batch i mod 2; exactly K steps between the barriers.
     two_lane = None
-    if (windows or args.workload == "tails") and not args.no_e2e:      # (profiling runs skip the legs that overlap launches)
+    if args.full and (windows or args.workload == "tails") and not args.no_e2e:      # (profiling runs skip the legs that overlap launches)
         batch2 = pack()
         if batch2.lane() != batch.lane():
             pair = (batch, batch2)
@@ -1655,10 +1694,12 @@ def main():
     dev_bytes = batch.device_bytes()
     wave_steps = batch.wave_steps()
     n_bad = int((res["status"] != 0).sum())
+    if args.dump_outputs and rank == 0:                  # (before the end-to-end legs: they fetch into these very arrays)
+        dump_gssw_outputs(args.dump_outputs, res, ops)
 
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu:      # the CPU leg (checker + baseline) runs at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:      # the CPU leg (checker + baseline) runs at N = 1 only
         ora_lib = os.path.join(ROOT, "oracle", "libvgoracle.so")
         ora = capi.Engine(capi.Scoring.simple(1, 4, 6, 1, 5), lib=ora_lib)     # the checker / CPU baseline leg
         cores = shard.usable_cpus()          # the affinity mask cut by the cgroup quota: what the CPU leg can really use
@@ -1722,7 +1763,7 @@ def main():
     t_warm = t_pipe = None
     if dist is not None:
         barrier()                                  # all ranks start their streaming legs together: they share the host
-    if not args.no_e2e:        # every rank streams its shard from host buffers; the slowest rank sets the rate
+    if args.full and not args.no_e2e:        # every rank streams its shard from host buffers; the slowest rank sets the rate
         def touched(a):                            # a second set of output arrays, pages already faulted in
             z = np.empty_like(a); z.view(np.uint8)[:] = 0
             return z
@@ -1836,7 +1877,7 @@ def main():
                   "traffic_source": out["roofline"].pop("traffic_source"), "cpu_baseline_notes": {k: cpu.pop(k) for k in ("cores_note",) if cpu and k in cpu}}
         print("[detail] " + json.dumps(detail), flush=True)
         side = {"headline_detail": detail, "secondary": []}
-        if world == 1 and args.workload == "linear" and not args.no_secondary and not args.no_cpu and os.environ.get("VGAMD_BENCH_SECONDARY", "1") != "0":
+        if args.full and world == 1 and args.workload == "linear" and not args.no_secondary and not args.no_cpu and os.environ.get("VGAMD_BENCH_SECONDARY", "1") != "0":
             if windows:
                 graph.close()
             eng.close()                                        # the headline is measured: its HBM goes back before the other legs start
@@ -1844,7 +1885,7 @@ def main():
                 side["secondary"].append(rec)
                 print("[secondary] " + json.dumps(rec), flush=True)
             out["secondary_file"] = "bench_secondary.json (%d records; also the `[secondary]` lines above)" % len(side["secondary"])
-        if args.workload == "linear":
+        if args.full and args.workload == "linear":
             try:
                 with open(os.path.join(ROOT, os.environ.get("VGAMD_BENCH_SIDE_FILE", "bench_secondary.json")), "w") as f:
                     json.dump(side, f, indent=1)

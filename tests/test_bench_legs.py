@@ -35,7 +35,7 @@ def test_default_run_ends_with_a_short_headline_line(emu_lib, tmp_path):
     env = dict(os.environ, VGAMD_BENCH_ONE_DEVICE="1", VGAMD_ENGINE_LIB=emu_lib, VGAMD_BENCH_SECONDARY_LEGS=json.dumps(legs), VGAMD_BENCH_SIDE_FILE=side)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "400", "--steps", "2", "--warmup", "1", "--cpu-sample", "400"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--reads", "400", "--steps", "2", "--warmup", "1", "--cpu-sample", "400"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.strip().splitlines()
@@ -54,6 +54,48 @@ def test_default_run_ends_with_a_short_headline_line(emu_lib, tmp_path):
     assert any(l.startswith("[detail] ") for l in lines)
     saved = json.load(open(side))
     assert saved["secondary"] == sec and "one_stream" in saved["headline_detail"]
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one(emu_lib, tmp_path):
+    """Without --full a run times --steps steps and prints the line, nothing more (no CPU leg, no secondary records, no side file);
+    --dump-outputs writes the last step's results — the same, run after run — and they are the oracle's."""
+    import numpy as np
+    from vg_amd import capi, workloads
+    from util import ORACLE_LIB
+    side = str(tmp_path / "side.json")
+    env = dict(os.environ, VGAMD_BENCH_ONE_DEVICE="1", VGAMD_ENGINE_LIB=emu_lib, VGAMD_BENCH_SIDE_FILE=side)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    dumps = []
+    for rep in range(2):
+        dump = tmp_path / ("out%d" % rep)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "400", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)],
+                             cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = out.stdout.strip().splitlines()
+        assert [l for l in lines if l.startswith("{")] == [lines[-1]]
+        d = json.loads(lines[-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+        assert d["unit"] == "reads/s" and d["dtype"] == "u16" and abs(d["value"] - 400 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert d["cpu_baseline"] is None and d["parity"] is None and d["end_to_end_warm_per_s"] is None and "secondary_file" not in d
+        assert not any(l.startswith("[secondary] ") for l in lines) and not os.path.exists(side)
+        files = sorted(dump.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrays = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys() and all((dumps[0][k] == dumps[1][k]).all() for k in dumps[0])
+    got = dumps[0]
+    assert (got["read_index"] == np.arange(400)).all() and (got["status"] == 0).all()
+    wl = workloads.LinearWorkload(400)
+    with capi.Engine(capi.Scoring.simple(1, 4, 6, 1, 5), lib=ORACLE_LIB).pack(wl, 48) as ob:
+        ob.run()
+        want, wops = ob.fetch()
+    for f in ("score", "status", "end_node", "end_offset", "end_read", "first_offset", "n_ops"):
+        assert (got[f] == want[f]).all(), f
+    want_ops = np.concatenate([wops[b:b + n] for b, n in zip(want["ops_begin"], want["n_ops"])])
+    assert len(want_ops) == len(got["op_node"]) > 400
+    assert (got["op_node"] == want_ops["node"]).all() and (got["op_len"] == want_ops["len"]).all() and (got["op_code"] == want_ops["op"]).all()
 
 
 def test_paired_leg_on_the_emulated_kernels(emu_lib):

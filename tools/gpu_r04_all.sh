@@ -28,7 +28,7 @@ b)
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r04b; mkdir -p $O
 timeout -s KILL 900 python -m pytest tests/test_gssw_wide.py tests/test_chain_alignment.py tests/test_gbwt_file.py tests/test_minimizer.py tests/test_gapless.py tests/test_giraffe_stage.py tests/test_gssw_gpu_parity.py -m gpu -q -x > $O/pytest_b.log 2>&1; echo "pytest rc=$?" >> $O/pytest_b.log; tail -5 $O/pytest_b.log
 t0=$(date +%s)
-timeout -s KILL 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"
+timeout -s KILL 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"
 python3 - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r04b/bench_default.json').read().strip().split('\n')[-1])
@@ -60,7 +60,7 @@ cd $GRAFT_REPO_ROOT; O=gpurun_out/r04d; mkdir -p $O
 timeout -s KILL 900 python -m pytest tests/test_gssw_gpu_parity.py tests/test_windows.py tests/test_reference_tap.py tests/test_tail_forest.py tests/test_giraffe_stage.py tests/test_alignment_batch.py -m gpu -q -x > $O/pytest_d.log 2>&1; echo "pytest rc=$?" >> $O/pytest_d.log; tail -5 $O/pytest_d.log
 for mode in rewalk codes; do
   if [ $mode = codes ]; then export VGAMD_TB_CODES=1; else unset VGAMD_TB_CODES; fi
-  timeout -s KILL 300 python bench.py --no-e2e --no-secondary --steps 10 --warmup 3 --cpu-sample 200000 > $O/bench_$mode.json 2> $O/bench_$mode.err
+  timeout -s KILL 300 python bench.py --full --no-e2e --no-secondary --steps 10 --warmup 3 --cpu-sample 200000 > $O/bench_$mode.json 2> $O/bench_$mode.err
   python3 -c "
 import json
 d=json.loads(open('$O/bench_$mode.json').read().strip().split('\n')[-1]); o=d['config']['one_stream']
@@ -73,7 +73,7 @@ cd $GRAFT_REPO_ROOT; O=gpurun_out/r04e; mkdir -p $O
 timeout -s KILL 900 python -m pytest tests/test_tb_rewalk.py tests/test_gssw_gpu_parity.py tests/test_windows.py tests/test_reference_tap.py tests/test_giraffe_stage.py -m gpu -q -x > $O/pytest_e.log 2>&1; echo "pytest rc=$?" >> $O/pytest_e.log; tail -5 $O/pytest_e.log
 for mode in rewalk codes; do
   if [ $mode = codes ]; then export VGAMD_TB_CODES=1; else unset VGAMD_TB_CODES; fi
-  timeout -s KILL 300 python bench.py --no-e2e --no-secondary --steps 10 --warmup 3 > $O/bench_$mode.json 2> $O/bench_$mode.err
+  timeout -s KILL 300 python bench.py --full --no-e2e --no-secondary --steps 10 --warmup 3 > $O/bench_$mode.json 2> $O/bench_$mode.err
   python3 -c "
 import json
 d=json.loads(open('$O/bench_$mode.json').read().strip().split('\n')[-1]); o=d['config']['one_stream']
@@ -88,7 +88,7 @@ f)
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r04f; mkdir -p $O
 timeout -s KILL 600 python -m pytest tests/test_tb_rewalk.py tests/test_windows.py -m gpu -q -x > $O/pytest_f.log 2>&1; echo "pytest rc=$?" >> $O/pytest_f.log; tail -3 $O/pytest_f.log
 export VGAMD_TB_REWALK=1
-timeout -s KILL 300 python bench.py --no-e2e --no-secondary --steps 10 --warmup 3 --cpu-sample 100000 > $O/bench_rewalk.json 2> $O/bench_rewalk.err
+timeout -s KILL 300 python bench.py --full --no-e2e --no-secondary --steps 10 --warmup 3 --cpu-sample 100000 > $O/bench_rewalk.json 2> $O/bench_rewalk.err
 python3 -c "
 import json
 d=json.loads(open('$O/bench_rewalk.json').read().strip().split('\n')[-1]); o=d['config']['one_stream']
@@ -116,7 +116,7 @@ h)
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r04h; mkdir -p $O
 timeout -s KILL 600 python -m pytest tests/test_tb_rewalk.py tests/test_windows.py tests/test_giraffe_stage.py -m gpu -q -x > $O/pytest_h.log 2>&1; echo "pytest rc=$?" >> $O/pytest_h.log; tail -3 $O/pytest_h.log
 export VGAMD_TB_REWALK=1
-timeout -s KILL 300 python bench.py --no-e2e --no-secondary --steps 10 --warmup 3 --cpu-sample 100000 > $O/bench_rewalk.json 2> $O/bench_rewalk.err
+timeout -s KILL 300 python bench.py --full --no-e2e --no-secondary --steps 10 --warmup 3 --cpu-sample 100000 > $O/bench_rewalk.json 2> $O/bench_rewalk.err
 python3 -c "
 import json
 d=json.loads(open('$O/bench_rewalk.json').read().strip().split('\n')[-1]); o=d['config']['one_stream']
@@ -178,7 +178,7 @@ last)
 # round 4, last GPU call: the first-pass traceback across nodes with several predecessors — gssw and window parity on the MI355X, the headline
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out/r04last; mkdir -p $O
 timeout -s KILL 55 python -m pytest tests/test_gssw_gpu_parity.py tests/test_windows.py -m gpu -q -x > $O/pytest.log 2>&1 < /dev/null; tail -2 $O/pytest.log
-timeout -s KILL 40 python3 bench.py --gpus 1 --steps 6 --warmup 2 --no-secondary --no-cpu > $O/bench_headline.json 2> $O/bench_headline.err < /dev/null; echo "bench rc=$?"
+timeout -s KILL 40 python3 bench.py --full --gpus 1 --steps 6 --warmup 2 --no-secondary --no-cpu > $O/bench_headline.json 2> $O/bench_headline.err < /dev/null; echo "bench rc=$?"
 python3 - <<'PY'
 import json, os
 O = os.environ.get('GRAFT_REPO_ROOT', '.') + '/gpurun_out/r04last'
@@ -334,7 +334,7 @@ w)
 # round 4: the headline after the walks' profile words moved into registers and the second fill's column cut — gssw parity tests, bench, kernel statistics
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out/r04w; mkdir -p $O
 timeout -s KILL 300 python -m pytest tests/test_gssw_gpu_parity.py -m gpu -q -x > $O/pytest_gssw.log 2>&1 < /dev/null; tail -2 $O/pytest_gssw.log
-timeout -s KILL 200 python3 bench.py --gpus 1 --steps 10 --warmup 3 --no-secondary > $O/bench_headline.json 2> $O/bench_headline.err < /dev/null; echo "bench rc=$?"
+timeout -s KILL 200 python3 bench.py --full --gpus 1 --steps 10 --warmup 3 --no-secondary > $O/bench_headline.json 2> $O/bench_headline.err < /dev/null; echo "bench rc=$?"
 ( cd /tmp && timeout -s KILL 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python $GRAFT_REPO_ROOT/bench.py --workload linear --reads 400000 --no-cpu --no-e2e --no-secondary --steps 3 --warmup 1 > $O/stats.log 2>&1 ) < /dev/null
 python3 - <<'PY'
 import json, glob, csv, os
@@ -387,7 +387,7 @@ cd $GRAFT_REPO_ROOT; O=$GRAFT_REPO_ROOT/gpurun_out/r04z; mkdir -p $O; export TMP
 timeout -s KILL 600 python -m pytest tests/test_gssw_gpu_parity.py tests/test_reference_tap.py tests/test_chain_alignment.py tests/test_giraffe_stage.py tests/test_alignment_batch.py -x -q -m gpu > $O/pytest.log 2>&1 < /dev/null; echo "pytest rc=$?"; tail -2 $O/pytest.log
 for v in spec two one; do
   unset VGAMD_WALK_ONE_PASS VGAMD_NO_SPEC_FILL; [ $v = one ] && export VGAMD_WALK_ONE_PASS=1; [ $v = two ] && export VGAMD_NO_SPEC_FILL=1
-  timeout -s KILL 200 python bench.py --gpus 1 --steps 10 --warmup 3 --no-secondary > $O/bench_$v.json 2> $O/bench_$v.err < /dev/null; echo "bench rc=$?"
+  timeout -s KILL 200 python bench.py --full --gpus 1 --steps 10 --warmup 3 --no-secondary > $O/bench_$v.json 2> $O/bench_$v.err < /dev/null; echo "bench rc=$?"
   timeout 30 python3 - <<PY
 import json
 d=json.loads(open("$O/bench_$v.json").read().strip().split("\n")[-1]); o=d["config"]["one_stream"]

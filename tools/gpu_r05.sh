@@ -14,7 +14,7 @@ case "$stage" in
     timeout 2400 python -m pytest tests -m gpu -x -q > "$out/pytest_gpu.log" 2>&1; echo "rc=$?" >> "$out/pytest_gpu.log"; tail -5 "$out/pytest_gpu.log"
     timeout 600 python __graft_entry__.py smoke > "$out/smoke.log" 2>&1; echo "rc=$?" >> "$out/smoke.log"; tail -2 "$out/smoke.log" ;;
   headline)       # the headline alone, and the speculation's feedback on a stream of reads that all miss (5 % indels)
-    timeout 600 python bench.py --no-secondary > "$out/bench_headline.json" 2> "$out/bench_headline.err"; tail -c 600 "$out/bench_headline.json"
+    timeout 600 python bench.py --full --no-secondary > "$out/bench_headline.json" 2> "$out/bench_headline.err"; tail -c 600 "$out/bench_headline.json"
     for pol in 0 2 1; do
       VGAMD_SPEC_POLICY=$pol timeout 600 python bench.py --reads 200000 --indel-rate 0.05 --steps 12 --warmup 0 --no-cpu --no-e2e --no-secondary \
           > "$out/bench_indel5_policy$pol.json" 2> "$out/bench_indel5_policy$pol.err"
@@ -193,6 +193,6 @@ for k in sorted(tot):
 PY
     done ;;
   default)        # what the driver runs: the headline + every secondary record
-    timeout 1700 python bench.py > "$out/bench_default_run.json" 2> "$out/bench_default_run.err"; tail -c 400 "$out/bench_default_run.json" ;;
+    timeout 1700 python bench.py --full > "$out/bench_default_run.json" 2> "$out/bench_default_run.err"; tail -c 400 "$out/bench_default_run.json" ;;
   *) echo "unknown stage $stage"; exit 2 ;;
 esac

@@ -14,7 +14,7 @@ case "$stage" in
   some_tests)     # named test files / -k expression: SOME="tests/test_x.py -k foo"
     timeout 1500 python -m pytest ${SOME:-tests} -m gpu -x -q > "$out/pytest_some.log" 2>&1; echo "rc=$?" >> "$out/pytest_some.log"; tail -8 "$out/pytest_some.log" ;;
   default)        # what the driver runs: the headline line + every secondary record
-    t0=$(date +%s); timeout 1700 python bench.py > "$out/bench_default_run.out" 2> "$out/bench_default_run.err"; echo "wall $(( $(date +%s) - t0 )) s"
+    t0=$(date +%s); timeout 1700 python bench.py --full > "$out/bench_default_run.out" 2> "$out/bench_default_run.err"; echo "wall $(( $(date +%s) - t0 )) s"
     cp bench_secondary.json "$out/" 2>/dev/null
     python - "$out/bench_default_run.out" <<'PY'
 import json, sys
