@@ -32,6 +32,10 @@
  * Also unpinned: N scores 0 against everything (as in vg's 5x5 matrix); best cell inside a
  * node = first column, then smallest query position; traceback preference
  * diagonal > deletion > insertion, gap open before extend, first explaining predecessor.
+ * Three more rules of the fill that no reference vector decides [PARITY-UNPINNED], stated as the definition's in tests/refdp.py (b) and
+ * counted by tests/test_definition.py: the leading insertion's limit is max_gap rounded UP to 8 rows (all vectors use max_gap far above
+ * their reads); a leading deletion from the root column is allowed at the ordinary gap price (no vector starts with one); the bonus is
+ * earned by the diagonal move onto the last query base only, not by inserting it (no vector ends in an insertion).
  */
 #include <stdint.h>
 #include <stdlib.h>

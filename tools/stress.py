@@ -9,6 +9,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 
 import gen
+import refdp
 import test_banded
 import test_gapless
 from vg_amd import capi
@@ -34,6 +35,12 @@ for sc in (capi.Scoring.simple(1, 4, 6, 1, 5), capi.Scoring.simple(2, 3, 5, 2, 7
         for i in range(ps.n):
             if rg["status"][i] != ro["status"][i] or rg["score"][i] != ro["score"][i] or (rg["score"][i] > 0 and capi.cigar_string(rg[i], og) != capi.cigar_string(ro[i], oo)):
                 bad += 1
+            elif i % 50 == 0 and rg["score"][i] > 0:      # a sample against the definition: the ops re-scored, the score the plain DP's optimum
+                m = problems[i]["flags"] & 15
+                try:
+                    refdp.check_alignment(problems[i], sc, m, rg[i], og[rg["ops_begin"][i]:rg["ops_begin"][i] + rg["n_ops"][i]], expect_optimum=refdp.optimum(problems[i], sc, m))
+                except AssertionError as e:
+                    print("  problem %d against the definition: %s" % (i, e)); bad += 1
         print("gssw mode=%s scoring=%s: %d problems, %d differ (%.1fs)" % (mode, list(sc.matrix[:2]), ps.n, bad, time.time() - t)); fails += bad
 
 # banded, all rows-per-lane classes, plain and quality-adjusted

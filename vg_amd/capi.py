@@ -125,6 +125,9 @@ def load_library(path=None):
     lib.vgk_gssw_fetch.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
     lib.vgk_gssw_align.argtypes = [vp, vp, u32, vp, vp, sz, ctypes.POINTER(sz)]
     lib.vgk_batch_free.argtypes = [vp]
+    if hasattr(lib, "vgk_gssw_wide_last"):                     # (the oracle has no wide route)
+        lib.vgk_gssw_wide_last.restype = ctypes.c_double
+        lib.vgk_gssw_wide_last.argtypes = [vp, ctypes.c_int]
     lib.vgk_xdrop_band_align.argtypes = [vp, vp, u32, vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64 * 2)]
     lib.vgk_graph_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
     lib.vgk_graph_destroy.argtypes = [vp]
@@ -396,6 +399,10 @@ class Engine:
         written = ctypes.c_size_t()
         self._check(self.lib.vgk_gssw_align(self.h, ps.ptr, ps.n, res.ctypes.data, ops.ctypes.data, cap, ctypes.byref(written)), "vgk_gssw_align")
         return res, ops[:written.value]
+
+    def wide_last(self, which):
+        """vgk_gssw_wide_last: the wide route's share of the last align_call (0 fill ms, 1 traceback ms, 2 cells, 3 traced cells, 4 launches)"""
+        return float(self.lib.vgk_gssw_wide_last(self.h, which))
 
     def xdrop_band_align(self, ps, out=None):
         """vgk_xdrop_band_align over a ProblemSet of VGK_XDROP_PINNED problems -> (results, ops, (cells in band, cells of the rectangles)).
