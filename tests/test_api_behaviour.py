@@ -263,3 +263,98 @@ def test_runs_longer_than_a_16_bit_op_length_are_refused_not_wrapped(emu_lib):
         capi.Engine(lib=emu_lib).align(problem_set([gssw]))
     res, _ = capi.Engine(lib=ORACLE_LIB).align(problem_set([gssw]))
     assert res["status"][0] == -7
+
+
+# ---- state one call leaves in HBM for the next survives every other family's calls on the same context ------------------------------
+# vgk_minimizer_seeds leaves its clusters for vgk_gapless_extend_seeded, an extension call its sets for vgk_tail_stage, vgk_wfa_extend its
+# results for vgk_chain_stitch's LINK pieces: all of it in the context's cached device buffers (vg_amd/csrc/scratch_slots.hpp), next to
+# the buffers of the families that keep nothing.  Between each producer and its consumer every such family runs once; the consumer's
+# answer is the oracle's all the same (the oracle keeps nothing between calls: its consumers go through the host).
+def state_left_in_hbm_survives_other_families(lib, monkeypatch, capfd, n_reads=300, n_wfa=300, n_other=120):
+    from gen import random_banded_problem
+    from test_chain_stitch import random_pieces
+    from test_wfa import random_wfa_case
+    from vg_amd import pipeline, workloads
+    sc = capi.Scoring.simple(1, 4, 6, 1, 5)
+    eng = capi.Engine(sc, lib=lib); ora = capi.Engine(sc, lib=ORACLE_LIB)
+    wl = workloads.GaplessWorkload(n_reads, seed=31, graph_bp=30000, inserted_reads=0.4)
+    flat, off = wl.gs.reads, wl.gs.read_off
+    hi, mi = eng.haplo_index(wl.nodes, wl.threads), eng.minimizer_index(wl.nodes, wl.threads)
+    ohi, omi = ora.haplo_index(wl.nodes, wl.threads), ora.minimizer_index(wl.nodes, wl.threads)
+
+    # the other families: banded (geometry on the host, geometry on the device: graphs without empty nodes), its k-best walk, the banded
+    # X-drop, the k-best pinned path, the minimizers of reads of any length
+    rng = np.random.default_rng(32)
+    banded = [p for p in (random_banded_problem(rng, p_empty=0.0) for _ in range(n_other // 2)) if all(len(s) for s in p["nodes"])]
+    bs = capi.BandedSet.from_lists(banded); bk = capi.BandedSet.from_lists(banded[:n_other // 4])
+    xs = problem_set([random_problem(rng, mode=capi.VGK_XDROP_PINNED) for _ in range(n_other)])
+    pinned = problem_set([random_problem(rng, max_nodes=8, max_node_len=10, max_read=40, mode=capi.VGK_GSSW_PINNED) for _ in range(n_other // 2)])
+
+    def others():
+        monkeypatch.setenv("VGAMD_BANDED_PIPELINE_MIN", "8"); monkeypatch.setenv("VGAMD_BANDED_TIMING", "1")
+        capfd.readouterr()
+        out = [eng.banded_align(bs)]
+        assert "device geometry" in capfd.readouterr().err                  # (the path was taken)
+        monkeypatch.setenv("VGAMD_BANDED_HOST_GEOMETRY", "1")
+        out.append(eng.banded_align(bs))
+        for name in ("VGAMD_BANDED_HOST_GEOMETRY", "VGAMD_BANDED_TIMING", "VGAMD_BANDED_PIPELINE_MIN"):
+            monkeypatch.delenv(name)
+        out += [eng.banded_align_multi(bk, 4), eng.xdrop_band_align(xs)[:2], eng.align_multi(pinned, 6)]
+        moff, recs = eng.minimizer_list(mi, flat, off)
+        assert len(recs) > n_reads
+        out += [(moff, recs), eng.minimizer_seeds_of(mi, recs, np.ones(len(recs), dtype=np.uint8))]
+        return [x.tobytes() for call in out for x in call]
+    first = others()
+    (rb, ob), (ro, oo) = eng.banded_align(bs), ora.banded_align(bs)           # (what runs in between is itself right)
+    assert (rb["status"] == ro["status"]).all() and (rb["score"] == ro["score"]).all() and ob.tobytes() == oo.tobytes()
+
+    # vgk_minimizer_seeds -> vgk_gapless_extend_seeded
+    oso, oseeds, _ = ora.minimizer_seeds(omi, ohi, flat, off)
+    want = ora.gapless_extend(ohi, capi.GaplessSet(flat, off, oseeds, oso))
+    so, _, _ = eng.minimizer_seeds(mi, hi, flat, off, keep_on_device=True)
+    assert (so == oso).all() and int(so[-1]) > n_reads
+    assert others() == first
+    got = eng.gapless_extend_seeded(hi, n_reads, int(so[-1]))
+    for name, x, y in zip(("results", "extensions", "nodes", "mismatches"), got, want):
+        assert len(x) == len(y), name
+        for f in (x.dtype.names or ()):
+            assert (x[f] == y[f]).all(), (name, f)
+        assert x.tobytes() == y.tobytes(), name
+
+    # vgk_gapless_extend -> vgk_tail_stage
+    olen = np.repeat(np.array([len(s) for s in wl.nodes]), 2)
+    stage = pipeline.align_stage(ora, ohi, olen, wl.gs)
+    res, ext, _, _ = eng.gapless_extend(hi, wl.gs)
+    assert (res["n_ext"] == stage["res"]["n_ext"]).all()
+    assert others() == first
+    ext_total, read_score, stats = eng.tail_stage(hi, wl.gs.n, int(res["n_ext"].sum()))
+    assert stats[0] == len(stage["tails"]["problems"]) > n_reads // 8 and stats[3] == 0
+    assert (ext_total == stage["ext_total"][:len(ext_total)]).all() and (read_score == stage["read_score"]).all()
+
+    # vgk_wfa_extend -> vgk_chain_stitch with LINK pieces
+    nodes, threads, wp = random_wfa_case(np.random.default_rng(33), n_wfa)
+    wi, owi = eng.haplo_index(nodes, threads), ora.haplo_index(nodes, threads)
+    wres = eng.wfa_extend(wi, wp)[0]; ores = ora.wfa_extend(owi, wp)[0]
+    both = ores.copy(); both["ok"] &= (wres["status"] == 0) & (wres["ok"] != 0)      # (the engine's tables decline a problem now and then: test_wfa.py)
+    assert both["ok"].sum() > 0.8 * (ores["ok"] != 0).sum()
+    pieces, poff, pn, pm, pe = random_pieces(np.random.default_rng(34), eng, wi, nodes, both, n_reads)
+    assert (pieces["kind"] == capi.PIECE_LINK).sum() > n_reads
+    assert others() == first
+    a = eng.chain_stitch(wi, pieces, poff, nodes=pn, mappings=pm, edits=pe)
+    b = ora.chain_stitch(owi, pieces, poff, nodes=pn, mappings=pm, edits=pe)
+    assert (b[0]["status"] == 0).sum() > n_reads // 2
+    for name, x, y in zip(("results", "mappings", "edits"), a, b):
+        assert len(x) == len(y), name
+        for f in (x.dtype.names or ()):
+            assert (x[f] == y[f]).all(), (name, f)
+        assert x.tobytes() == y.tobytes(), name
+
+
+def test_state_left_in_hbm_survives_other_families_on_the_emulated_engine(emu_lib, monkeypatch, capfd):
+    state_left_in_hbm_survives_other_families(emu_lib, monkeypatch, capfd)
+
+
+@pytest.mark.gpu
+def test_state_left_in_hbm_survives_other_families_on_the_gpu(monkeypatch, capfd):
+    from util import ENGINE_LIB
+    state_left_in_hbm_survives_other_families(ENGINE_LIB, monkeypatch, capfd)

@@ -227,12 +227,12 @@ void prepare(const vgk_ctx* ctx, const vgk_banded_problem& p, Prep& hp, Scratch&
 }
 
 // device scratch cached on the context (grow-only)
-inline void* ensure(vgk_ctx* ctx, int slot, uint64_t bytes) { return ctx->ensure_scratch(slot, bytes); }
-template <class T> int stage(vgk_ctx* ctx, int slot, const T* v, size_t count, const T*& out) {
-    void* d = ensure(ctx, slot, std::max<size_t>(count, 1) * sizeof(T));
+// (vgk_ctx::scratch_dev with this file's error convention: no memory is VGK_ENOMEM, a failed upload its own code; nothing goes up when count == 0)
+template <class T> int stage(vgk_ctx* ctx, Slot slot, const T* v, size_t count, const T*& out) {
+    T* d = ctx->scratch_dev<T>(slot, nullptr, std::max<size_t>(count, 1) * sizeof(T));
     if (!d) return VGK_ENOMEM;
     if (count) { int rc = ctx->be->upload(d, v, count * sizeof(T)); if (rc) return rc; }
-    out = (const T*)d;
+    out = d;
     return VGK_OK;
 }
 // host arenas kept on the context between calls: uninitialised storage, so a warm call neither zero-fills nor page-faults
@@ -252,12 +252,11 @@ struct HostArenas {
     ~HostArenas() { if (be) for (void* e : ev) if (e) be->event_destroy(e); }
 };
 enum { S_PROBS, S_ORDER, S_NODES, S_SEEDS, S_POOL, S_STARTS, S_READS, S_QUALS, S_GRAPH, S_MAT, S_TB, S_LAST, S_OPS, S_DENSE, S_RESULTS, S_COUNT };
-constexpr int S_SCORES = 31;          // k-best mode: the full score matrices (slots 15..30 belong to gapless_api.cpp)
-constexpr int S_SET1 = 124;           // the pipelined path's second sub-batch in flight: slots S_SET1 + S_*
 enum { G_PROBS, G_NODELEN, G_PREDOFF, G_PREDIDX, G_TMP, G_OUT, G_COUNT };
-constexpr int G_SET0 = 140, G_SET1 = 146;     // the device-geometry path's raw arrays, per sub-batch in flight
+// a sub-batch's buffers: BANDED<set>_PROBS + S_*, BGEOM<set>_PROBS + G_* (scratch_slots.hpp; the pipelined paths keep two sub-batches in flight)
 constexpr int BANDED_NOT_HERE = 10000;        // banded_align_device_geometry: this call is for the host-geometry path (never leaves the library)
-static_assert(S_COUNT <= 15 && S_SCORES < (int)(sizeof(vgk_ctx::scratch) / sizeof(vgk_ctx::DevBuf)) && S_SET1 + S_COUNT <= (int)(sizeof(vgk_ctx::scratch) / sizeof(vgk_ctx::DevBuf)), "scratch slots");
+static_assert(BANDED0_END - BANDED0_PROBS == S_COUNT && BANDED1_END - BANDED1_PROBS == S_COUNT, "scratch_slots.hpp: the BANDED0_* / BANDED1_* runs name S_*");
+static_assert(BGEOM0_END - BGEOM0_PROBS == G_COUNT && BGEOM1_END - BGEOM1_PROBS == G_COUNT, "scratch_slots.hpp: the BGEOM0_* / BGEOM1_* runs name G_*");
 
 
 
@@ -611,19 +610,19 @@ static int banded_align_impl(vgk_ctx* ctx, const vgk_banded_problem* problems, u
                 for (int g = 0; g < 5; ++g) std::memcpy(mat_rows + BMAT_ROWS_AT + 8 * g, ctx->sc.matrix + 5 * g, 5);
             }
             const int8_t* mat = qa ? ctx->qmat.data() : mat_rows;
-            if ((rc = stage(ctx, S_PROBS, (const BProb*)probs, m, P.probs)) || (rc = stage(ctx, S_ORDER, (const uint32_t*)order, m, P.order)) ||
-                (rc = stage(ctx, S_NODES, (const BNode*)nodes, n_nodes, P.nodes)) || (rc = stage(ctx, S_SEEDS, (const BSeed*)seeds, n_seeds, P.seeds)) ||
-                (rc = stage(ctx, S_POOL, (const uint32_t*)pool, n_pool, P.pool)) || (rc = stage(ctx, S_STARTS, (const BStart*)starts, n_starts, P.starts)) ||
-                (rc = stage(ctx, S_READS, (const uint8_t*)reads, n_read, P.reads)) || (qa && (rc = stage(ctx, S_QUALS, (const uint8_t*)quals, n_read, P.quals))) ||
-                (rc = stage(ctx, S_GRAPH, (const uint8_t*)graph, n_graph, P.graph)) || (rc = stage(ctx, S_MAT, mat, qa ? 6400 : BMAT_BYTES, P.mat))) return rc;
+            if ((rc = stage(ctx, BANDED0_PROBS + S_PROBS, (const BProb*)probs, m, P.probs)) || (rc = stage(ctx, BANDED0_PROBS + S_ORDER, (const uint32_t*)order, m, P.order)) ||
+                (rc = stage(ctx, BANDED0_PROBS + S_NODES, (const BNode*)nodes, n_nodes, P.nodes)) || (rc = stage(ctx, BANDED0_PROBS + S_SEEDS, (const BSeed*)seeds, n_seeds, P.seeds)) ||
+                (rc = stage(ctx, BANDED0_PROBS + S_POOL, (const uint32_t*)pool, n_pool, P.pool)) || (rc = stage(ctx, BANDED0_PROBS + S_STARTS, (const BStart*)starts, n_starts, P.starts)) ||
+                (rc = stage(ctx, BANDED0_PROBS + S_READS, (const uint8_t*)reads, n_read, P.reads)) || (qa && (rc = stage(ctx, BANDED0_PROBS + S_QUALS, (const uint8_t*)quals, n_read, P.quals))) ||
+                (rc = stage(ctx, BANDED0_PROBS + S_GRAPH, (const uint8_t*)graph, n_graph, P.graph)) || (rc = stage(ctx, BANDED0_PROBS + S_MAT, mat, qa ? 6400 : BMAT_BYTES, P.mat))) return rc;
             lap("h2d");
             P.go = ctx->sc.gap_open; P.ge = ctx->sc.gap_extend; P.n = m;
-            P.tb = (uint8_t*)ensure(ctx, S_TB, std::max<uint64_t>(tb_bytes, 256));
-            P.last = (int32_t*)ensure(ctx, S_LAST, std::max<uint64_t>(last_elems, 64) * sizeof(int32_t));
-            P.ops = (vgk_op*)ensure(ctx, S_OPS, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
-            P.dense = (vgk_op*)ensure(ctx, S_DENSE, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
-            uint8_t* rblock = (uint8_t*)ensure(ctx, S_RESULTS, (size_t)m * sizeof(BResult) + 64);
-            if (multi) P.scores = (int32_t*)ensure(ctx, S_SCORES, std::max<uint64_t>(tb_bytes, 256) * 3 * sizeof(int32_t));
+            P.tb = (uint8_t*)ctx->ensure_scratch(BANDED0_PROBS + S_TB, std::max<uint64_t>(tb_bytes, 256));
+            P.last = (int32_t*)ctx->ensure_scratch(BANDED0_PROBS + S_LAST, std::max<uint64_t>(last_elems, 64) * sizeof(int32_t));
+            P.ops = (vgk_op*)ctx->ensure_scratch(BANDED0_PROBS + S_OPS, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
+            P.dense = (vgk_op*)ctx->ensure_scratch(BANDED0_PROBS + S_DENSE, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
+            uint8_t* rblock = (uint8_t*)ctx->ensure_scratch(BANDED0_PROBS + S_RESULTS, (size_t)m * sizeof(BResult) + 64);
+            if (multi) P.scores = (int32_t*)ctx->ensure_scratch(BANDED_SCORES, std::max<uint64_t>(tb_bytes, 256) * 3 * sizeof(int32_t));
             if (!P.tb || !P.last || !P.ops || !P.dense || !rblock || (multi && !P.scores)) return VGK_ENOMEM;
             P.dense_count = (unsigned long long*)rblock; P.results = (BResult*)(rblock + 64);
             if ((rc = be->zero(rblock, 64))) return rc;
@@ -656,17 +655,12 @@ static int banded_align_impl(vgk_ctx* ctx, const vgk_banded_problem* problems, u
                         ops_off[a + 1] = ops_off[a] + 2ull * max_alt_alns * probs[a].ops_cap;
                     }
                     const uint64_t n_res = (uint64_t)m * max_alt_alns, slots = max_alt_alns + 1;
-                    auto up = [&](int slot, const void* src, size_t bytes) -> void* {
-                        void* d = ctx->ensure_scratch(slot, std::max<size_t>(bytes, 16)); if (!d) return nullptr;
-                        if (src && bytes && be->upload(d, src, bytes)) return nullptr;
-                        return d;
-                    };
-                    Q.pool = (BmTrace*)up(72, nullptr, sizeof(BmTrace) * slots * m); Q.order = (uint32_t*)up(73, nullptr, sizeof(uint32_t) * slots * m);
-                    Q.sp_off = (const uint32_t*)up(74, sp_off.data(), sizeof(uint32_t) * (n_starts + 1)); Q.sp_len = (const uint32_t*)up(75, sp_len.data(), sizeof(uint32_t) * (n_starts + 1));
-                    Q.prefix = (const uint32_t*)up(76, prefix.data(), sizeof(uint32_t) * prefix.size()); Q.host_only = (const uint8_t*)up(77, host_only.data(), m);
-                    Q.results = (vgk_result*)up(78, nullptr, sizeof(vgk_result) * n_res); Q.n_alignments = (uint32_t*)up(79, nullptr, sizeof(uint32_t) * m);
-                    Q.ops = (vgk_op*)up(80, nullptr, sizeof(vgk_op) * ops_off[m]); Q.ops_off = (const uint64_t*)up(81, ops_off.data(), sizeof(uint64_t) * m);
-                    Q.status = (int32_t*)up(82, nullptr, sizeof(int32_t) * m);
+                    Q.pool = ctx->scratch_dev<BmTrace>(BKBEST_POOL, nullptr, sizeof(BmTrace) * slots * m); Q.order = ctx->scratch_dev<uint32_t>(BKBEST_ORDER, nullptr, sizeof(uint32_t) * slots * m);
+                    Q.sp_off = ctx->scratch_dev<const uint32_t>(BKBEST_SP_OFF, sp_off.data(), sizeof(uint32_t) * (n_starts + 1)); Q.sp_len = ctx->scratch_dev<const uint32_t>(BKBEST_SP_LEN, sp_len.data(), sizeof(uint32_t) * (n_starts + 1));
+                    Q.prefix = ctx->scratch_dev<const uint32_t>(BKBEST_PREFIX, prefix.data(), sizeof(uint32_t) * prefix.size()); Q.host_only = ctx->scratch_dev<const uint8_t>(BKBEST_HOST_ONLY, host_only.data(), m);
+                    Q.results = ctx->scratch_dev<vgk_result>(BKBEST_RESULTS, nullptr, sizeof(vgk_result) * n_res); Q.n_alignments = ctx->scratch_dev<uint32_t>(BKBEST_N_ALIGNMENTS, nullptr, sizeof(uint32_t) * m);
+                    Q.ops = ctx->scratch_dev<vgk_op>(BKBEST_OPS, nullptr, sizeof(vgk_op) * ops_off[m]); Q.ops_off = ctx->scratch_dev<const uint64_t>(BKBEST_OPS_OFF, ops_off.data(), sizeof(uint64_t) * m);
+                    Q.status = ctx->scratch_dev<int32_t>(BKBEST_STATUS, nullptr, sizeof(int32_t) * m);
                     if (!Q.pool || !Q.order || !Q.sp_off || !Q.sp_len || !Q.prefix || !Q.host_only || !Q.results || !Q.n_alignments || !Q.ops || !Q.ops_off || !Q.status) return VGK_ENOMEM;
                     if ((rc = be->zero(Q.results, sizeof(vgk_result) * n_res))) return rc;
                     if ((rc = be->run_banded_multi(Q))) return rc;
@@ -675,14 +669,14 @@ static int banded_align_impl(vgk_ctx* ctx, const vgk_banded_problem* problems, u
                     if ((rc = be->download(dcnt.data(), Q.n_alignments, sizeof(uint32_t) * m))) return rc;
                     std::vector<vgk_result> dres(n_res); std::vector<vgk_op> dops2;
                     const uint32_t blocks = (uint32_t)((n_res + Backend::OPS_SCAN_BLOCK - 1) / Backend::OPS_SCAN_BLOCK);
-                    uint32_t* offs = (uint32_t*)up(83, nullptr, sizeof(uint32_t) * n_res);
-                    uint32_t* sums = (uint32_t*)up(84, nullptr, sizeof(uint32_t) * (blocks + 8));
+                    uint32_t* offs = ctx->scratch_dev<uint32_t>(BKBEST_OFFS, nullptr, sizeof(uint32_t) * n_res);
+                    uint32_t* sums = ctx->scratch_dev<uint32_t>(BKBEST_SUMS, nullptr, sizeof(uint32_t) * (blocks + 8));
                     if (!offs || !sums) return VGK_ENOMEM;
                     uint64_t total = 0;
                     rc = be->ops_offsets(Q.results, (uint32_t)n_res, offs, sums, &total);
                     if (rc == VGK_OK) {
-                        vgk_result* pres_d = (vgk_result*)up(85, nullptr, sizeof(vgk_result) * n_res);
-                        vgk_op* pops_d = (vgk_op*)up(86, nullptr, sizeof(vgk_op) * std::max<uint64_t>(total, 1));
+                        vgk_result* pres_d = ctx->scratch_dev<vgk_result>(BKBEST_PRES, nullptr, sizeof(vgk_result) * n_res);
+                        vgk_op* pops_d = ctx->scratch_dev<vgk_op>(BKBEST_POPS, nullptr, sizeof(vgk_op) * std::max<uint64_t>(total, 1));
                         if (!pres_d || !pops_d) return VGK_ENOMEM;
                         if ((rc = be->ops_gather(Q.results, Q.ops, (uint32_t)n_res, offs, sums, pres_d, pops_d))) return rc;
                         if ((rc = be->sync_fetch())) return rc;
@@ -969,7 +963,7 @@ static int banded_align_pipelined(vgk_ctx* ctx, const vgk_banded_problem* proble
     auto launch = [&](BSub& S, int set) -> int {
         const uint32_t m = S.m;
         if (!m) return VGK_OK;
-        PinnedSet& A = H.set[set]; const int base = set ? S_SET1 : 0;
+        PinnedSet& A = H.set[set]; const Slot base = set ? BANDED1_PROBS : BANDED0_PROBS;
         const uint64_t n_nodes = S.sizes[0], n_seeds = S.sizes[1], n_pool = S.sizes[2], n_starts = S.sizes[3], n_read = S.sizes[4], n_graph = S.sizes[5], tb_bytes = S.sizes[6], last_elems = S.sizes[7], ops_total = S.sizes[8];
         const uint32_t par = (S.i / quarter) & 1u;
         const BProb* probs = A.probs.p; const uint32_t* order = A.order.p; const BNode* nodes = H.qnodes[par].p + qoff[par][S.i - qlo[par]]; const BSeed* seeds = A.seeds.p; const uint32_t* pool = A.pool.p; const BStart* starts = A.starts.p;
@@ -982,11 +976,11 @@ static int banded_align_pipelined(vgk_ctx* ctx, const vgk_banded_problem* proble
             (rc = stage(ctx, base + S_READS, (const uint8_t*)reads, n_read, P.reads)) || (qa && (rc = stage(ctx, base + S_QUALS, (const uint8_t*)quals, n_read, P.quals))) ||
             (rc = stage(ctx, base + S_GRAPH, (const uint8_t*)graph, n_graph, P.graph)) || (rc = stage(ctx, base + S_MAT, mat, qa ? 6400 : BMAT_BYTES, P.mat))) return rc;
         P.go = ctx->sc.gap_open; P.ge = ctx->sc.gap_extend; P.n = m;
-        P.tb = (uint8_t*)ensure(ctx, base + S_TB, std::max<uint64_t>(tb_bytes, 256));
-        P.last = (int32_t*)ensure(ctx, base + S_LAST, std::max<uint64_t>(last_elems, 64) * sizeof(int32_t));
-        P.ops = (vgk_op*)ensure(ctx, base + S_OPS, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
-        P.dense = (vgk_op*)ensure(ctx, base + S_DENSE, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
-        uint8_t* rblock = (uint8_t*)ensure(ctx, base + S_RESULTS, (size_t)m * sizeof(BResult) + 64);
+        P.tb = (uint8_t*)ctx->ensure_scratch(base + S_TB, std::max<uint64_t>(tb_bytes, 256));
+        P.last = (int32_t*)ctx->ensure_scratch(base + S_LAST, std::max<uint64_t>(last_elems, 64) * sizeof(int32_t));
+        P.ops = (vgk_op*)ctx->ensure_scratch(base + S_OPS, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
+        P.dense = (vgk_op*)ctx->ensure_scratch(base + S_DENSE, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
+        uint8_t* rblock = (uint8_t*)ctx->ensure_scratch(base + S_RESULTS, (size_t)m * sizeof(BResult) + 64);
         if (!P.tb || !P.last || !P.ops || !P.dense || !rblock) return VGK_ENOMEM;
         P.dense_count = (unsigned long long*)rblock; P.results = (BResult*)(rblock + 64);
         if ((rc = be->zero(rblock, 64))) return rc;
@@ -1128,7 +1122,7 @@ static int banded_align_device_geometry(vgk_ctx* ctx, const vgk_banded_problem* 
     struct Sums { uint64_t v[6]; };                              // problems, nodes, edges, read bases, graph bases, (unused)
     // ---- first half of a sub-batch: sizes, gather + checks, geometry on the device, placement
     auto build = [&](uint32_t from, BSub& S, int set) -> int {
-        PinnedSet& A = H.set[set]; HostArenas::GeomSet& G = H.gset[set]; const int gbase = set ? G_SET1 : G_SET0, base = set ? S_SET1 : 0;
+        PinnedSet& A = H.set[set]; HostArenas::GeomSet& G = H.gset[set]; const Slot gbase = set ? BGEOM1_PROBS : BGEOM0_PROBS, base = set ? BANDED1_PROBS : BANDED0_PROBS;
         const uint32_t limit = std::min<uint32_t>(n, (from / quarter + 1u) * quarter), cnt = limit - from;
         S.i = from; S.j = limit; S.owner.clear(); S.launches.clear(); S.m = 0;
         const uint32_t n_chunks = chunk_count(cnt);
@@ -1199,14 +1193,14 @@ static int banded_align_device_geometry(vgk_ctx* ctx, const vgk_banded_problem* 
         });
         // the geometry: raw arrays up on the side stream, a lane per problem behind them, the 40 bytes per problem back
         BGeomParams Q{}; Q.n = m;
-        void* d_gprobs = ensure(ctx, gbase + G_PROBS, (uint64_t)m * sizeof(BGeomProb)); void* d_len = ensure(ctx, gbase + G_NODELEN, (all.v[1] + 1) * 4);
-        void* d_poff = ensure(ctx, gbase + G_PREDOFF, (all.v[1] + m + 1) * 4); void* d_pidx = ensure(ctx, gbase + G_PREDIDX, (all.v[2] + 1) * 4);
-        void* d_tmp = ensure(ctx, gbase + G_TMP, (all.v[1] + 1) * 12); void* d_out = ensure(ctx, gbase + G_OUT, (uint64_t)m * sizeof(BGeomOut));
-        void* d_nodes = ensure(ctx, base + S_NODES, (all.v[1] + 1) * sizeof(BNode)); void* d_seeds = ensure(ctx, base + S_SEEDS, (all.v[2] + 1) * sizeof(BSeed));
-        void* d_starts = ensure(ctx, base + S_STARTS, (all.v[1] + 1) * sizeof(BStart)); void* d_pool = ensure(ctx, base + S_POOL, 16);
+        void* d_gprobs = ctx->ensure_scratch(gbase + G_PROBS, (uint64_t)m * sizeof(BGeomProb)); void* d_len = ctx->ensure_scratch(gbase + G_NODELEN, (all.v[1] + 1) * 4);
+        void* d_poff = ctx->ensure_scratch(gbase + G_PREDOFF, (all.v[1] + m + 1) * 4); void* d_pidx = ctx->ensure_scratch(gbase + G_PREDIDX, (all.v[2] + 1) * 4);
+        void* d_tmp = ctx->ensure_scratch(gbase + G_TMP, (all.v[1] + 1) * 12); void* d_out = ctx->ensure_scratch(gbase + G_OUT, (uint64_t)m * sizeof(BGeomOut));
+        void* d_nodes = ctx->ensure_scratch(base + S_NODES, (all.v[1] + 1) * sizeof(BNode)); void* d_seeds = ctx->ensure_scratch(base + S_SEEDS, (all.v[2] + 1) * sizeof(BSeed));
+        void* d_starts = ctx->ensure_scratch(base + S_STARTS, (all.v[1] + 1) * sizeof(BStart)); void* d_pool = ctx->ensure_scratch(base + S_POOL, 16);
         if (!d_gprobs || !d_len || !d_poff || !d_pidx || !d_tmp || !d_out || !d_nodes || !d_seeds || !d_starts || !d_pool) return VGK_ENOMEM;
         // (the coded reads and bases travel on the side stream as well, under the fills of the sub-batch before ...
-        void* d_reads = ensure(ctx, base + S_READS, all.v[3] + 1); void* d_quals = qa ? ensure(ctx, base + S_QUALS, all.v[3] + 1) : nullptr; void* d_graph = ensure(ctx, base + S_GRAPH, all.v[4] + 1);
+        void* d_reads = ctx->ensure_scratch(base + S_READS, all.v[3] + 1); void* d_quals = qa ? ctx->ensure_scratch(base + S_QUALS, all.v[3] + 1) : nullptr; void* d_graph = ctx->ensure_scratch(base + S_GRAPH, all.v[4] + 1);
         if (!d_reads || (qa && !d_quals) || !d_graph) return VGK_ENOMEM;
         int rc;
         if ((rc = be->upload_side(d_gprobs, gprobs, (size_t)m * sizeof(BGeomProb))) || (rc = be->upload_side(d_len, node_len, (size_t)all.v[1] * 4)) ||
@@ -1283,18 +1277,18 @@ static int banded_align_device_geometry(vgk_ctx* ctx, const vgk_banded_problem* 
     // ---- ... the rest up on the main stream, the fills and the tracebacks behind it
     auto launch = [&](BSub& S, int set) -> int {
         if (!S.m) return VGK_OK;
-        PinnedSet& A = H.set[set]; const int base = set ? S_SET1 : 0;
+        PinnedSet& A = H.set[set]; const Slot base = set ? BANDED1_PROBS : BANDED0_PROBS;
         BandedParams& P = S.P;
         const uint64_t tb_bytes = S.sizes[6], last_elems = S.sizes[7], ops_total = S.sizes[8];
         int rc;
         if ((rc = stage(ctx, base + S_PROBS, (const BProb*)A.probs2.p, std::max<uint32_t>(P.n, 1), P.probs)) || (rc = stage(ctx, base + S_ORDER, (const uint32_t*)A.order.p, std::max<uint32_t>(P.n, 1), P.order)) ||
             (rc = stage(ctx, base + S_MAT, mat, qa ? 6400 : BMAT_BYTES, P.mat))) return rc;
         P.go = ctx->sc.gap_open; P.ge = ctx->sc.gap_extend;
-        P.tb = (uint8_t*)ensure(ctx, base + S_TB, std::max<uint64_t>(tb_bytes, 256));
-        P.last = (int32_t*)ensure(ctx, base + S_LAST, std::max<uint64_t>(last_elems, 64) * sizeof(int32_t));
-        P.ops = (vgk_op*)ensure(ctx, base + S_OPS, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
-        P.dense = (vgk_op*)ensure(ctx, base + S_DENSE, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
-        uint8_t* rblock = (uint8_t*)ensure(ctx, base + S_RESULTS, (size_t)S.m * sizeof(BResult) + 64);
+        P.tb = (uint8_t*)ctx->ensure_scratch(base + S_TB, std::max<uint64_t>(tb_bytes, 256));
+        P.last = (int32_t*)ctx->ensure_scratch(base + S_LAST, std::max<uint64_t>(last_elems, 64) * sizeof(int32_t));
+        P.ops = (vgk_op*)ctx->ensure_scratch(base + S_OPS, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
+        P.dense = (vgk_op*)ctx->ensure_scratch(base + S_DENSE, std::max<uint64_t>(ops_total, 1) * sizeof(vgk_op));
+        uint8_t* rblock = (uint8_t*)ctx->ensure_scratch(base + S_RESULTS, (size_t)S.m * sizeof(BResult) + 64);
         if (!P.tb || !P.last || !P.ops || !P.dense || !rblock) return VGK_ENOMEM;
         P.dense_count = (unsigned long long*)rblock; P.results = (BResult*)(rblock + 64);
         if ((rc = be->zero(rblock, 64)) || (rc = be->main_after_side())) return rc;

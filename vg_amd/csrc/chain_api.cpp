@@ -56,9 +56,9 @@ int vgk_chain_stitch(vgk_ctx* ctx, const vgk_haplo* index, const vgk_chain_piece
     if (n_nodes) std::memcpy(up + b_off + b_pc, nodes, sizeof(uint32_t) * n_nodes);
     if (n_mappings) std::memcpy(up + b_off + b_pc + b_nd, mappings, sizeof(vgk_chain_mapping) * n_mappings);
     if (n_edits) std::memcpy(up + b_off + b_pc + b_nd + b_mp, edits, sizeof(uint32_t) * n_edits);
-    char* d_up = (char*)ctx->ensure_scratch(140, up_bytes);
-    uint32_t* d_tab = (uint32_t*)ctx->ensure_scratch(141, sizeof(uint32_t) * 8 * (uint64_t)R);      // bound | slot | count | out_slot, two halves each
-    vgk_chain_result* d_res = (vgk_chain_result*)ctx->ensure_scratch(142, sizeof(vgk_chain_result) * 2 * (uint64_t)n_reads);
+    char* d_up = (char*)ctx->ensure_scratch(CHAIN_UP, up_bytes);
+    uint32_t* d_tab = (uint32_t*)ctx->ensure_scratch(CHAIN_TAB, sizeof(uint32_t) * 8 * (uint64_t)R);      // bound | slot | count | out_slot, two halves each
+    vgk_chain_result* d_res = (vgk_chain_result*)ctx->ensure_scratch(CHAIN_RES, sizeof(vgk_chain_result) * 2 * (uint64_t)n_reads);
     if (!d_up || !d_tab || !d_res) return VGK_ENOMEM;
     int rc;
     be->watch(0);
@@ -80,8 +80,8 @@ int vgk_chain_stitch(vgk_ctx* ctx, const vgk_haplo* index, const vgk_chain_piece
     const uint64_t most_e = n_edits + (uint64_t)n_nodes + n_pieces + (links ? ctx->wfa_out.path_cap + ctx->wfa_out.edit_cap : 0);
     if (most_m > 0xfffffff0ull || most_e > 0xfffffff0ull) return VGK_ETOOBIG;
     const uint64_t work_m = tails[0], work_e = tails[1];
-    P.work_m = (vgk_chain_mapping*)ctx->ensure_scratch(143, sizeof(vgk_chain_mapping) * (work_m + 1));
-    P.work_e = (uint32_t*)ctx->ensure_scratch(144, sizeof(uint32_t) * (work_e + 1));
+    P.work_m = (vgk_chain_mapping*)ctx->ensure_scratch(CHAIN_WORK_M, sizeof(vgk_chain_mapping) * (work_m + 1));
+    P.work_e = (uint32_t*)ctx->ensure_scratch(CHAIN_WORK_E, sizeof(uint32_t) * (work_e + 1));
     if (!P.work_m || !P.work_e) return VGK_ENOMEM;
     // 2. the composition; exact sizes and their prefix sums
     if ((rc = be->run_chain_stitch(P, CS_STITCH))) return rc;
@@ -93,8 +93,8 @@ int vgk_chain_stitch(vgk_ctx* ctx, const vgk_haplo* index, const vgk_chain_piece
     if (written) { written[0] = total_m; written[1] = total_e; }
     // 3. dense output in read order, as much of it as the caller has room for
     P.out_m_cap = std::min<uint64_t>(mapping_cap, total_m); P.out_e_cap = std::min<uint64_t>(edit_cap, total_e);
-    P.out_m = (vgk_chain_mapping*)ctx->ensure_scratch(145, sizeof(vgk_chain_mapping) * (P.out_m_cap + 1));
-    P.out_e = (uint32_t*)ctx->ensure_scratch(146, sizeof(uint32_t) * (P.out_e_cap + 1));
+    P.out_m = (vgk_chain_mapping*)ctx->ensure_scratch(CHAIN_OUT_M, sizeof(vgk_chain_mapping) * (P.out_m_cap + 1));
+    P.out_e = (uint32_t*)ctx->ensure_scratch(CHAIN_OUT_E, sizeof(uint32_t) * (P.out_e_cap + 1));
     if (!P.out_m || !P.out_e) return VGK_ENOMEM;
     if ((rc = be->run_chain_stitch(P, CS_GATHER))) return rc;
     be->watch(1);

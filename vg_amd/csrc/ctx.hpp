@@ -4,6 +4,7 @@
 #include <mutex>
 #include <vector>
 #include "backend.hpp"
+#include "scratch_slots.hpp"
 
 // page-locked host staging kept on the context between calls: uninitialised, no page faults, full-rate DMA in both directions
 template <class T> struct PinnedBuf {
@@ -118,8 +119,8 @@ struct vgk_ctx {
     uint64_t multi_host_walks = 0;       // problems of the last vgk_gssw_align_multi whose alternates a host thread walked
     // device scratch kept between vgk_banded_align calls (grow-only; released with the context)
     struct DevBuf { void* p = nullptr; uint64_t bytes = 0; };
-    DevBuf scratch[160];           // 140..149 chain_api.cpp; 150..157 minimizer_api.cpp (reads of any length); 66, 67 wfa_api.cpp (the sequences as the caller holds them, their offsets); 88..99 gssw_wide_api.cpp; 65 wfa_api.cpp (producers_done); 72..83 gssw_multi_api.cpp (the walk on the device); 0..14 + 31 banded_api.cpp (+ 124..138: its second sub-batch in flight), 15..30 + 59, 60 gapless_api.cpp, 32..39 + 61..63 wfa_api.cpp, 40..47 gssw_multi_api.cpp / xdrop_band_api.cpp (+ 48, 49, 87; its second sub-batch in flight: 100..123), 50..54 tail_api.cpp, 55..58 minimizer_api.cpp
-    void* ensure_scratch(int slot, uint64_t bytes) {
+    DevBuf scratch[SLOT_COUNT];    // scratch_slots.hpp names them
+    void* ensure_scratch(Slot slot, uint64_t bytes) {
         DevBuf& b = scratch[slot];
         if (b.p && b.bytes >= bytes) return b.p;
         if (b.p) { be->sync(); be->release(b.p); b.p = nullptr; b.bytes = 0; }
@@ -132,6 +133,13 @@ struct vgk_ctx {
         }
         return b.p;
     }
+    // the staging step of every family: the slot at max(bytes, 16), `src` uploaded into it when there is one; nullptr when either fails
+    void* scratch_dev(Slot slot, const void* src, size_t bytes) {
+        void* d = ensure_scratch(slot, bytes > 16 ? bytes : 16);
+        if (d && src && bytes && be->upload(d, src, bytes)) return nullptr;
+        return d;
+    }
+    template <class T> T* scratch_dev(Slot slot, const void* src, size_t bytes) { return (T*)scratch_dev(slot, src, bytes); }
     // Device arenas of freed gssw batches, kept for the next pack (callers hold `mu`): allocating the 35 GB of a million-read batch
     // takes the runtime 0.9-1.8 s, more than packing, aligning and fetching it.  Requests are rounded up by an eighth so that the
     // next, slightly larger batch still fits; a block serves requests down to half its size; at most 192 blocks / half of HBM stay (a batch holds 13 arenas, a fetch 4 more, a forest 9, a tail stage 13 and the packer 13 temporaries: with 64 the stage of §17 kept dropping and re-allocating blocks).

@@ -340,18 +340,13 @@ void vgk_haplo_destroy(vgk_haplo* h) {
 }
 
 // Everything behind "the inputs are on the device": the three kernels, the sets put in problem order on the device, the way back.
-// P carries index, probs, reads, seeds, order, n; n_seed = seeds of the whole batch; `slot` = the next free scratch slot.
-static int gapless_run_and_fetch(vgk_ctx* ctx, GaplessParams& P, uint32_t n, uint64_t n_seed, int next_slot, GaplessHost& H, GLap& lap,
+// P carries index, probs, reads, seeds, order, n; n_seed = seeds of the whole batch.
+static int gapless_run_and_fetch(vgk_ctx* ctx, GaplessParams& P, uint32_t n, uint64_t n_seed, GaplessHost& H, GLap& lap,
                                  vgk_gapless_result* results, vgk_extension* extensions, size_t ext_cap,
                                  uint32_t* nodes, size_t nodes_cap, uint32_t* mismatches, size_t mism_cap, size_t written[3], const bool defer = false) {
     Backend* be = ctx->be.get();
     auto cleanup = [&](int rc) { return rc; };
     { const int rc0 = ctx->finish_deferred(); if (rc0) return rc0; }         // (an earlier call's sets still on their way use the same staging)
-    auto dev = [&](const void* src, size_t bytes) -> void* {
-        void* d = ctx->ensure_scratch(next_slot++, std::max<size_t>(bytes, 16)); if (!d) return nullptr;
-        if (src && bytes && be->upload(d, src, bytes)) return nullptr;
-        return d;
-    };
     P.match = ctx->sc.matrix[0]; P.mismatch = -ctx->sc.matrix[1]; P.bonus = ctx->sc.full_length_bonus;
     // dense outputs: at most one extension per seed; nodes / mismatches sized generously and checked on the device
     const uint64_t cap_e = n_seed + 1, cap_n = std::min<uint64_t>(n_seed * G_PATH, std::max<uint64_t>(n_seed * 16 + 1024, nodes_cap)) + 1,
@@ -363,17 +358,15 @@ static int gapless_run_and_fetch(vgk_ctx* ctx, GaplessParams& P, uint32_t n, uin
     uint64_t per_cu = 1024;          // 16 wavefronts per CU: the kernel is built for at most 128 VGPRs (__launch_bounds__(64, 4))
     if (const char* e = std::getenv("VGAMD_GAPLESS_THREADS_PER_CU")) per_cu = (uint64_t)std::max(64, std::atoi(e));
     const uint32_t threads = (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max(1, be->compute_units()) * per_cu);
-    { vgk_ctx::DevBuf& b = ctx->scratch[15];
-      const uint64_t want = sizeof(GScratch) * (uint64_t)threads;
-      (void)b; P.scratch = (GScratch*)ctx->ensure_scratch(15, want);
-      P.cold = (GCold*)ctx->ensure_scratch(30, sizeof(GCold) * (uint64_t)threads); }
-    P.results = (vgk_gapless_result*)dev(nullptr, sizeof(vgk_gapless_result) * n);
-    P.ext = (vgk_extension*)dev(nullptr, sizeof(vgk_extension) * cap_e);
-    P.nodes = (uint32_t*)dev(nullptr, sizeof(uint32_t) * cap_n);
-    P.mism = (uint32_t*)dev(nullptr, sizeof(uint32_t) * cap_m);
-    P.counters = (unsigned long long*)dev(nullptr, 256);
-    P.retry = (uint8_t*)ctx->ensure_scratch(60, (size_t)n + 16);        // (a slot of its own: 31 is the banded k-best's score planes)
-    P.winners = (GExt*)dev(nullptr, sizeof(GExt) * (n_seed + 1));          // the searches' winners wait here for the rules kernel (248 B each; only the used ones are touched)
+    P.scratch = (GScratch*)ctx->ensure_scratch(GAPLESS_SCRATCH, sizeof(GScratch) * (uint64_t)threads);
+    P.cold = (GCold*)ctx->ensure_scratch(GAPLESS_COLD, sizeof(GCold) * (uint64_t)threads);
+    P.results = ctx->scratch_dev<vgk_gapless_result>(GAPLESS_RESULTS, nullptr, sizeof(vgk_gapless_result) * n);
+    P.ext = ctx->scratch_dev<vgk_extension>(GAPLESS_EXT, nullptr, sizeof(vgk_extension) * cap_e);
+    P.nodes = ctx->scratch_dev<uint32_t>(GAPLESS_NODES, nullptr, sizeof(uint32_t) * cap_n);
+    P.mism = ctx->scratch_dev<uint32_t>(GAPLESS_MISM, nullptr, sizeof(uint32_t) * cap_m);
+    P.counters = ctx->scratch_dev<unsigned long long>(GAPLESS_COUNTERS, nullptr, 256);
+    P.retry = (uint8_t*)ctx->ensure_scratch(GAPLESS_RETRY, (size_t)n + 16);
+    P.winners = ctx->scratch_dev<GExt>(GAPLESS_WINNERS, nullptr, sizeof(GExt) * (n_seed + 1));          // the searches' winners wait here for the rules kernel (248 B each; only the used ones are touched)
     if (!P.winners || !P.probs || !P.reads || !P.seeds || !P.order || !P.scratch || !P.cold || !P.results || !P.ext || !P.nodes || !P.mism || !P.counters) return cleanup(VGK_ENOMEM);
     int rc;
     if ((rc = be->zero(P.counters, 256))) return cleanup(rc);
@@ -394,11 +387,11 @@ static int gapless_run_and_fetch(vgk_ctx* ctx, GaplessParams& P, uint32_t n, uin
     // (gapless_device.hpp), then three contiguous arrays come down through page-locked staging
     GOrderParams O{};
     O.n = n; O.res = P.results; O.ext = P.ext; O.nodes = P.nodes; O.mism = P.mism;
-    uint32_t* tab = (uint32_t*)ctx->ensure_scratch(26, sizeof(uint32_t) * 6 * ((size_t)n + 1));
-    O.res_out = (vgk_gapless_result*)ctx->ensure_scratch(27, sizeof(vgk_gapless_result) * (size_t)n);
-    O.ext_out = (vgk_extension*)ctx->ensure_scratch(28, sizeof(vgk_extension) * (ne + 1));
-    O.nodes_out = (uint32_t*)ctx->ensure_scratch(29, sizeof(uint32_t) * (nn + nm + 2));
-    O.read_of = (uint32_t*)ctx->ensure_scratch(59, sizeof(uint32_t) * (ne + 1));
+    uint32_t* tab = (uint32_t*)ctx->ensure_scratch(GAPLESS_TAB, sizeof(uint32_t) * 6 * ((size_t)n + 1));
+    O.res_out = (vgk_gapless_result*)ctx->ensure_scratch(GAPLESS_RES_OUT, sizeof(vgk_gapless_result) * (size_t)n);
+    O.ext_out = (vgk_extension*)ctx->ensure_scratch(GAPLESS_EXT_OUT, sizeof(vgk_extension) * (ne + 1));
+    O.nodes_out = (uint32_t*)ctx->ensure_scratch(GAPLESS_NODES_OUT, sizeof(uint32_t) * (nn + nm + 2));
+    O.read_of = (uint32_t*)ctx->ensure_scratch(GAPLESS_READ_OF, sizeof(uint32_t) * (ne + 1));
     if (!tab || !O.res_out || !O.ext_out || !O.nodes_out || !O.read_of) return cleanup(VGK_ENOMEM);
     O.mism_out = O.nodes_out + nn + 1;
     const size_t n1 = (size_t)n + 1;
@@ -545,28 +538,22 @@ int vgk_gapless_extend(vgk_ctx* ctx, const vgk_haplo* index, const vgk_gapless_p
     });
     lap("descriptors; reads and seeds gathered unless they lie in a row");
     // device buffers are kept on the context between calls (grow-only)
-    int next_slot = 16;
     auto cleanup = [&](int rc) { return rc; };
-    auto dev = [&](const void* src, size_t bytes) -> void* {
-        void* d = ctx->ensure_scratch(next_slot++, std::max<size_t>(bytes, 16)); if (!d) return nullptr;
-        if (src && bytes && be->upload(d, src, bytes)) return nullptr;
-        return d;
-    };
     GaplessParams P{};
     { const bool runs = index->merged && index->search_merged;
       P.index = runs ? index->merged->dev : index->dev; P.orig = index->dev; P.merge = runs ? index->merge : GMerge{}; P.n = n; }
-    P.probs = (const GProb*)dev(probs.data(), sizeof(GProb) * n);
-    P.reads = (const char*)dev(nullptr, n_read + 16);                  // 8 bytes of padding at either end
+    P.probs = ctx->scratch_dev<const GProb>(GAPLESS_PROBS, probs.data(), sizeof(GProb) * n);
+    P.reads = ctx->scratch_dev<const char>(GAPLESS_READS, nullptr, n_read + 16);                  // 8 bytes of padding at either end
     if (P.reads && n_read && be->upload(const_cast<char*>(P.reads) + 8, reads_in_a_row ? read0 : reads + 8, n_read)) return VGK_ENODEV;
     if (P.reads && (be->mask_reads(const_cast<char*>(P.reads), n_read + 16) || be->zero(const_cast<char*>(P.reads), 8) || be->zero(const_cast<char*>(P.reads) + 8 + n_read, 8))) return VGK_ENODEV;
-    P.seeds = (const vgk_seed*)dev(nullptr, sizeof(vgk_seed) * (n_seed + 1));
+    P.seeds = ctx->scratch_dev<const vgk_seed>(GAPLESS_SEEDS, nullptr, sizeof(vgk_seed) * (n_seed + 1));
     if (P.seeds && n_seed && be->upload(const_cast<vgk_seed*>(P.seeds), seeds_in_a_row ? seed0 : seeds, sizeof(vgk_seed) * n_seed)) return VGK_ENODEV;
     // processing order: by the node of the first seed (a counting sort; reads without seeds last).  Results do not depend on it —
     // problems are independent and the sets are handed back in problem order below — but reads that sit next to each other in a
     // wavefront now walk the same records and bases, which the L2 then serves (FETCH_SIZE per million reads: see DESIGN.md §11)
     // (made on the device from the uploaded descriptors and seeds: a kernel for the keys and a stable radix sort, as for the seeded form)
     if (!P.probs || !P.reads || !P.seeds) return VGK_ENOMEM;
-    uint32_t* d_sort = (uint32_t*)ctx->ensure_scratch(next_slot++, sizeof(uint32_t) * 4 * (size_t)n);       // key, index, sorted key, order
+    uint32_t* d_sort = (uint32_t*)ctx->ensure_scratch(GAPLESS_SORT, sizeof(uint32_t) * 4 * (size_t)n);       // key, index, sorted key, order
     if (!d_sort) return VGK_ENOMEM;
     if (std::getenv("VGAMD_GAPLESS_UNSORTED")) {
         std::vector<uint32_t> order(n); for (uint32_t i = 0; i < n; ++i) order[i] = i;
@@ -581,7 +568,7 @@ int vgk_gapless_extend(vgk_ctx* ctx, const vgk_haplo* index, const vgk_gapless_p
         if (rc) return rc;
     }
     P.order = d_sort + 3 * (size_t)n;
-    return gapless_run_and_fetch(ctx, P, n, n_seed, next_slot, H, lap, results, extensions, ext_cap, nodes, nodes_cap, mismatches, mism_cap, written,
+    return gapless_run_and_fetch(ctx, P, n, n_seed, H, lap, results, extensions, ext_cap, nodes, nodes_cap, mismatches, mism_cap, written,
                                  (problems[0].flags & VGK_GAPLESS_DEFER) != 0);        // (a property of the call, carried by its first problem)
 } catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }      // (no exception leaves the C ABI)
 
@@ -605,9 +592,8 @@ int vgk_gapless_extend_seeded(vgk_ctx* ctx, const vgk_haplo* index, uint32_t max
     if (!ctx->gapless_host) ctx->gapless_host = std::make_shared<GaplessHost>();
     GaplessHost& H = *static_cast<GaplessHost*>(ctx->gapless_host.get());
     const uint64_t n_seed = ctx->seeded.n_seeds;
-    int next_slot = 16;
-    GProb* d_probs = (GProb*)ctx->ensure_scratch(next_slot++, sizeof(GProb) * (size_t)n);
-    uint32_t* d_sort = (uint32_t*)ctx->ensure_scratch(next_slot++, sizeof(uint32_t) * 4 * (size_t)n);      // key, index, sorted key, order
+    GProb* d_probs = (GProb*)ctx->ensure_scratch(GAPLESS_PROBS, sizeof(GProb) * (size_t)n);
+    uint32_t* d_sort = (uint32_t*)ctx->ensure_scratch(GAPLESS_SORT, sizeof(uint32_t) * 4 * (size_t)n);      // key, index, sorted key, order
     if (!d_probs || !d_sort) return VGK_ENOMEM;
     const uint32_t buckets = index->n_oriented / 2 + 2;
     int bits = 1; while ((1u << bits) < buckets && bits < 32) ++bits;
@@ -623,7 +609,7 @@ int vgk_gapless_extend_seeded(vgk_ctx* ctx, const vgk_haplo* index, uint32_t max
       P.index = runs ? index->merged->dev : index->dev; P.orig = index->dev; P.merge = runs ? index->merge : GMerge{}; P.n = n; }
     P.probs = d_probs; P.reads = ctx->seeded.reads; P.seeds = ctx->seeded.seeds; P.order = d_sort + 3 * (size_t)n;
     lap("descriptors and order on the device");
-    return gapless_run_and_fetch(ctx, P, n, n_seed, next_slot, H, lap, results, extensions, ext_cap, nodes, nodes_cap, mismatches, mism_cap, written, (flags & VGK_GAPLESS_DEFER) != 0);
+    return gapless_run_and_fetch(ctx, P, n, n_seed, H, lap, results, extensions, ext_cap, nodes, nodes_cap, mismatches, mism_cap, written, (flags & VGK_GAPLESS_DEFER) != 0);
 } catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }      // (no exception leaves the C ABI)
 
 int vgk_gapless_rerun(vgk_ctx* ctx) try {

@@ -273,17 +273,12 @@ int vgk_gssw_align_multi(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_
             });
             GsswMatrixParams P{};
             P.n = m; P.go = ctx->sc.gap_open; P.ge = ctx->sc.gap_extend;
-            auto dev = [&](int slot, const void* src, size_t bytes) -> void* {
-                void* d = ctx->ensure_scratch(slot, std::max<size_t>(bytes, 16)); if (!d) return nullptr;
-                if (src && bytes && be->upload(d, src, bytes)) return nullptr;
-                return d;
-            };
-            P.probs = (MProb*)dev(40, probs, sizeof(MProb) * m);
-            P.reads = (const uint8_t*)dev(41, reads, n_read); P.quals = qa ? (const uint8_t*)dev(42, quals, n_read) : nullptr;
-            P.graph = (const uint8_t*)dev(43, graph, n_graph); P.nodes = (const MNode*)dev(44, nodes, sizeof(MNode) * n_nodes);
-            P.preds = (const uint32_t*)dev(45, preds, sizeof(uint32_t) * n_preds);
-            P.mat = (const int8_t*)dev(46, qa ? ctx->qmat.data() : ctx->sc.matrix, qa ? 6400 : 25);
-            P.cells = (int32_t*)dev(47, nullptr, sizeof(int32_t) * n_cells);
+            P.probs = ctx->scratch_dev<MProb>(MULTI_PROBS, probs, sizeof(MProb) * m);
+            P.reads = ctx->scratch_dev<const uint8_t>(MULTI_READS, reads, n_read); P.quals = qa ? ctx->scratch_dev<const uint8_t>(MULTI_QUALS, quals, n_read) : nullptr;
+            P.graph = ctx->scratch_dev<const uint8_t>(MULTI_GRAPH, graph, n_graph); P.nodes = ctx->scratch_dev<const MNode>(MULTI_NODES, nodes, sizeof(MNode) * n_nodes);
+            P.preds = ctx->scratch_dev<const uint32_t>(MULTI_PREDS, preds, sizeof(uint32_t) * n_preds);
+            P.mat = ctx->scratch_dev<const int8_t>(MULTI_MAT, qa ? ctx->qmat.data() : ctx->sc.matrix, qa ? 6400 : 25);
+            P.cells = ctx->scratch_dev<int32_t>(MULTI_CELLS, nullptr, sizeof(int32_t) * n_cells);
             if (!P.probs || !P.reads || (qa && !P.quals) || !P.graph || !P.nodes || !P.preds || !P.mat || !P.cells) return VGK_ENOMEM;
             int rc;
             if ((rc = be->run_gssw_matrix(P))) return rc;
@@ -305,14 +300,14 @@ int vgk_gssw_align_multi(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_
                 const uint64_t n_res = (uint64_t)m * max_alt_alns, slots = max_alt_alns + 2;
                 GsswMultiParams Q{};
                 Q.M = P; Q.max_alt = max_alt_alns;
-                Q.pinning = (const uint8_t*)dev(72, pin.data(), n_nodes);
-                Q.pool = (MtAlt*)dev(73, nullptr, sizeof(MtAlt) * slots * m);
-                Q.order = (uint32_t*)dev(74, nullptr, sizeof(uint32_t) * slots * m);
-                Q.results = (vgk_result*)dev(75, nullptr, sizeof(vgk_result) * n_res);
-                Q.n_alignments = (uint32_t*)dev(76, nullptr, sizeof(uint32_t) * m);
-                Q.status = (int32_t*)dev(77, nullptr, sizeof(int32_t) * m);
-                Q.ops = (vgk_op*)dev(78, nullptr, sizeof(vgk_op) * ops_off[m]);
-                Q.ops_off = (const uint64_t*)dev(79, ops_off.data(), sizeof(uint64_t) * m);
+                Q.pinning = ctx->scratch_dev<const uint8_t>(MULTI_PINNING, pin.data(), n_nodes);
+                Q.pool = ctx->scratch_dev<MtAlt>(MULTI_POOL, nullptr, sizeof(MtAlt) * slots * m);
+                Q.order = ctx->scratch_dev<uint32_t>(MULTI_ORDER, nullptr, sizeof(uint32_t) * slots * m);
+                Q.results = ctx->scratch_dev<vgk_result>(MULTI_RESULTS, nullptr, sizeof(vgk_result) * n_res);
+                Q.n_alignments = ctx->scratch_dev<uint32_t>(MULTI_N_ALIGNMENTS, nullptr, sizeof(uint32_t) * m);
+                Q.status = ctx->scratch_dev<int32_t>(MULTI_STATUS, nullptr, sizeof(int32_t) * m);
+                Q.ops = ctx->scratch_dev<vgk_op>(MULTI_OPS, nullptr, sizeof(vgk_op) * ops_off[m]);
+                Q.ops_off = ctx->scratch_dev<const uint64_t>(MULTI_OPS_OFF, ops_off.data(), sizeof(uint64_t) * m);
                 if (!Q.pinning || !Q.pool || !Q.order || !Q.results || !Q.n_alignments || !Q.status || !Q.ops || !Q.ops_off) return VGK_ENOMEM;
                 if ((rc = be->zero(Q.results, sizeof(vgk_result) * n_res))) return rc;
                 if ((rc = be->run_gssw_multi(Q))) return rc;
@@ -322,14 +317,14 @@ int vgk_gssw_align_multi(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_
                 // the ops packed behind each other on the device (the windows are mostly air), then results + ops back
                 std::vector<vgk_result> dres(n_res); std::vector<vgk_op> dops;
                 const uint32_t blocks = (uint32_t)((n_res + Backend::OPS_SCAN_BLOCK - 1) / Backend::OPS_SCAN_BLOCK);
-                uint32_t* offs = (uint32_t*)dev(80, nullptr, sizeof(uint32_t) * n_res);
-                uint32_t* sums = (uint32_t*)dev(81, nullptr, sizeof(uint32_t) * (blocks + 8));
+                uint32_t* offs = ctx->scratch_dev<uint32_t>(MULTI_OFFS, nullptr, sizeof(uint32_t) * n_res);
+                uint32_t* sums = ctx->scratch_dev<uint32_t>(MULTI_SUMS, nullptr, sizeof(uint32_t) * (blocks + 8));
                 uint64_t total = 0;
                 if (!offs || !sums) return VGK_ENOMEM;
                 rc = be->ops_offsets(Q.results, (uint32_t)n_res, offs, sums, &total);
                 if (rc == VGK_OK) {
-                    vgk_result* pres_d = (vgk_result*)dev(82, nullptr, sizeof(vgk_result) * n_res);
-                    vgk_op* pops_d = (vgk_op*)dev(83, nullptr, sizeof(vgk_op) * std::max<uint64_t>(total, 1));
+                    vgk_result* pres_d = ctx->scratch_dev<vgk_result>(MULTI_PRES, nullptr, sizeof(vgk_result) * n_res);
+                    vgk_op* pops_d = ctx->scratch_dev<vgk_op>(MULTI_POPS, nullptr, sizeof(vgk_op) * std::max<uint64_t>(total, 1));
                     if (!pres_d || !pops_d) return VGK_ENOMEM;
                     if ((rc = be->ops_gather(Q.results, Q.ops, (uint32_t)n_res, offs, sums, pres_d, pops_d))) return rc;
                     if ((rc = be->sync_fetch())) return rc;

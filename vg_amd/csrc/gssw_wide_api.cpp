@@ -148,28 +148,23 @@ int vgk::wide_align(vgk_ctx* ctx, const vgk_gssw_problem* problems, const uint32
         if (n) {
             if (A.colinfo.size() >= (1ull << 32) || A.prof.size() >= (1ull << 32) || A.ops >= (1ull << 32)) return VGK_ETOOBIG;
             WideParams P{};
-            auto dev = [&](int slot, const void* src, uint64_t bytes) -> void* {
-                void* d = ctx->ensure_scratch(slot, std::max<uint64_t>(bytes, 16)); if (!d) return nullptr;
-                if (src && bytes && be->upload(d, src, bytes)) return nullptr;
-                return d;
-            };
             std::vector<uint32_t> order(n);
             uint32_t n8 = 0;
             for (uint32_t k = 0; k < n; ++k) if (A.probs[k].K == 8) order[n8++] = k;
             { uint32_t at = n8; for (uint32_t k = 0; k < n; ++k) if (A.probs[k].K != 8) order[at++] = k; }
             A.colinfo.resize(A.colinfo.size() + 8, (uint8_t)CI_INVALID);
-            P.probs = (const WideProb*)dev(88, A.probs.data(), sizeof(WideProb) * n); P.n = n;
-            P.order = (const uint32_t*)dev(89, order.data(), 4ull * n);
-            P.colinfo = (const uint8_t*)dev(90, A.colinfo.data(), A.colinfo.size());
-            P.prof = (const uint32_t*)dev(91, A.prof.data(), 4ull * A.prof.size());
-            P.nodes = (const NodeRec*)dev(92, A.nodes.data(), sizeof(NodeRec) * A.nodes.size());
-            P.preds = (const uint32_t*)dev(93, A.preds.data(), 4ull * A.preds.size());
-            P.scratch = (WPair*)dev(94, nullptr, sizeof(WPair) * (A.scratch + 1));
-            P.carry = (WPair*)dev(95, nullptr, sizeof(WPair) * (A.carry + 1));
-            P.tb = (uint32_t*)dev(96, nullptr, 4ull * (A.tb + 1));
-            P.best = (unsigned long long*)dev(97, nullptr, 8ull * (n + 1));
-            P.results = (vgk_result*)dev(98, nullptr, sizeof(vgk_result) * (n + 1ull));
-            P.ops = (vgk_op*)dev(99, nullptr, sizeof(vgk_op) * (A.ops + 1));
+            P.probs = ctx->scratch_dev<const WideProb>(WIDE_PROBS, A.probs.data(), sizeof(WideProb) * n); P.n = n;
+            P.order = ctx->scratch_dev<const uint32_t>(WIDE_ORDER, order.data(), 4ull * n);
+            P.colinfo = ctx->scratch_dev<const uint8_t>(WIDE_COLINFO, A.colinfo.data(), A.colinfo.size());
+            P.prof = ctx->scratch_dev<const uint32_t>(WIDE_PROF, A.prof.data(), 4ull * A.prof.size());
+            P.nodes = ctx->scratch_dev<const NodeRec>(WIDE_NODES, A.nodes.data(), sizeof(NodeRec) * A.nodes.size());
+            P.preds = ctx->scratch_dev<const uint32_t>(WIDE_PREDS, A.preds.data(), 4ull * A.preds.size());
+            P.scratch = ctx->scratch_dev<WPair>(WIDE_SCRATCH, nullptr, sizeof(WPair) * (A.scratch + 1));
+            P.carry = ctx->scratch_dev<WPair>(WIDE_CARRY, nullptr, sizeof(WPair) * (A.carry + 1));
+            P.tb = ctx->scratch_dev<uint32_t>(WIDE_TB, nullptr, 4ull * (A.tb + 1));
+            P.best = ctx->scratch_dev<unsigned long long>(WIDE_BEST, nullptr, 8ull * (n + 1));
+            P.results = ctx->scratch_dev<vgk_result>(WIDE_RESULTS, nullptr, sizeof(vgk_result) * (n + 1ull));
+            P.ops = ctx->scratch_dev<vgk_op>(WIDE_OPS, nullptr, sizeof(vgk_op) * (A.ops + 1));
             if (!P.probs || !P.order || !P.colinfo || !P.prof || !P.nodes || !P.preds || !P.scratch || !P.carry || !P.tb || !P.best || !P.results || !P.ops) return VGK_ENOMEM;
             P.bias = (int32_t)ctx->bias; P.go = ctx->sc.gap_open; P.ge = ctx->sc.gap_extend;
             int rc = be->zero(P.best, 8ull * (n + 1));

@@ -151,9 +151,9 @@ int vgk_minimizer_seeds(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vgk_h
     std::lock_guard<std::mutex> stage(ctx->stage_mu);
     std::lock_guard<std::mutex> lk(ctx->mu);
     ctx->seeded.valid = false;
-    char* d_reads = (char*)ctx->ensure_scratch(55, bytes + 32);              // 8 bytes of padding at either end, as the extension kernels want them
-    uint64_t* d_off = (uint64_t*)ctx->ensure_scratch(56, sizeof(uint64_t) * ((size_t)n + 1));
-    uint32_t* d_tab = (uint32_t*)ctx->ensure_scratch(57, sizeof(uint32_t) * 3 * ((size_t)n + 1));
+    char* d_reads = (char*)ctx->ensure_scratch(SEEDED_READS, bytes + 32);              // 8 bytes of padding at either end, as the extension kernels want them
+    uint64_t* d_off = (uint64_t*)ctx->ensure_scratch(SEEDED_READ_OFF, sizeof(uint64_t) * ((size_t)n + 1));
+    uint32_t* d_tab = (uint32_t*)ctx->ensure_scratch(SEEDED_TAB, sizeof(uint32_t) * 3 * ((size_t)n + 1));
     if (!d_reads || !d_off || !d_tab) return VGK_ENOMEM;
     const size_t n1 = (size_t)n + 1;
     std::vector<uint64_t> rel(n1);
@@ -188,7 +188,7 @@ int vgk_minimizer_seeds(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vgk_h
     const bool keep_on_device = !seeds && !seeds_cap;                         // the caller goes on with vgk_gapless_extend_seeded: the seeds need not come down
     if (!keep_on_device && (total > seeds_cap || (total && !seeds))) return VGK_EOPS;
     // (the seed buffer exists even for a batch without a single seed: the seeded extension call tells "no seeds" from "no memory" by it)
-    vgk_seed* d_seeds = (vgk_seed*)ctx->ensure_scratch(58, sizeof(vgk_seed) * std::max<size_t>(total, 1));
+    vgk_seed* d_seeds = (vgk_seed*)ctx->ensure_scratch(SEEDED_SEEDS, sizeof(vgk_seed) * std::max<size_t>(total, 1));
     if (!d_seeds) return VGK_ENOMEM;
     P.seeds = d_seeds;
     if (total) {
@@ -231,10 +231,10 @@ int vgk_minimizer_list(vgk_ctx* ctx, const vgk_minimizer_index* ix, const char* 
     if (items.size() > 0xfffffff0ull) return VGK_ETOOBIG;
     const uint32_t n_items = (uint32_t)items.size();
     const size_t n1 = (size_t)n + 1, m1 = (size_t)n_items + 1;
-    char* d_reads = (char*)ctx->ensure_scratch(150, bytes + 32);
-    uint64_t* d_off = (uint64_t*)ctx->ensure_scratch(151, sizeof(uint64_t) * n1);
-    uint32_t* d_tab = (uint32_t*)ctx->ensure_scratch(152, sizeof(uint32_t) * 2 * m1);
-    MzListItem* d_items = (MzListItem*)ctx->ensure_scratch(157, sizeof(MzListItem) * std::max<size_t>(n_items, 1));
+    char* d_reads = (char*)ctx->ensure_scratch(MZLIST_READS, bytes + 32);
+    uint64_t* d_off = (uint64_t*)ctx->ensure_scratch(MZLIST_READ_OFF, sizeof(uint64_t) * n1);
+    uint32_t* d_tab = (uint32_t*)ctx->ensure_scratch(MZLIST_TAB, sizeof(uint32_t) * 2 * m1);
+    MzListItem* d_items = (MzListItem*)ctx->ensure_scratch(MZLIST_ITEMS, sizeof(MzListItem) * std::max<size_t>(n_items, 1));
     if (!d_reads || !d_off || !d_tab || !d_items) return VGK_ENOMEM;
     std::vector<uint64_t> rel(n1);
     for (size_t i = 0; i < n1; ++i) rel[i] = read_off[i] - read_off[0];
@@ -255,7 +255,7 @@ int vgk_minimizer_list(vgk_ctx* ctx, const vgk_minimizer_index* ix, const char* 
     if (written) *written = total;
     if (total > cap) return VGK_EOPS;
     if (!total) return VGK_OK;
-    vgk_read_minimizer* d_out = (vgk_read_minimizer*)ctx->ensure_scratch(153, sizeof(vgk_read_minimizer) * total);
+    vgk_read_minimizer* d_out = (vgk_read_minimizer*)ctx->ensure_scratch(MZLIST_MINIMIZERS, sizeof(vgk_read_minimizer) * total);
     if (!d_out) return VGK_ENOMEM;
     P.out = d_out; P.pass = 2;
     if ((rc = be->run_minimizer_list(P))) return rc;
@@ -272,9 +272,9 @@ int vgk_minimizer_seeds_of(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vg
     Backend* be = ctx->be.get();
     std::lock_guard<std::mutex> lk(ctx->mu);
     const uint32_t n = (uint32_t)n_minimizers; const size_t n1 = (size_t)n + 1;
-    vgk_read_minimizer* d_min = (vgk_read_minimizer*)ctx->ensure_scratch(153, sizeof(vgk_read_minimizer) * n_minimizers);
-    uint8_t* d_take = (uint8_t*)ctx->ensure_scratch(154, n_minimizers + 16);
-    uint32_t* d_tab = (uint32_t*)ctx->ensure_scratch(155, sizeof(uint32_t) * 2 * n1);
+    vgk_read_minimizer* d_min = (vgk_read_minimizer*)ctx->ensure_scratch(MZLIST_MINIMIZERS, sizeof(vgk_read_minimizer) * n_minimizers);
+    uint8_t* d_take = (uint8_t*)ctx->ensure_scratch(MZLIST_TAKE, n_minimizers + 16);
+    uint32_t* d_tab = (uint32_t*)ctx->ensure_scratch(MZLIST_SEED_TAB, sizeof(uint32_t) * 2 * n1);
     if (!d_min || !d_take || !d_tab) return VGK_ENOMEM;
     MzSeedsOfParams P{};
     P.index = ix->dev; P.mins = d_min; P.take = d_take; P.n = n; P.counts = d_tab; P.first = d_tab + n1; P.pass = 1;
@@ -294,7 +294,7 @@ int vgk_minimizer_seeds_of(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vg
     if (written) *written = total;
     if (total > cap) return VGK_EOPS;
     if (!total) return VGK_OK;
-    vgk_seed* d_out = (vgk_seed*)ctx->ensure_scratch(156, sizeof(vgk_seed) * total);
+    vgk_seed* d_out = (vgk_seed*)ctx->ensure_scratch(MZLIST_SEEDS, sizeof(vgk_seed) * total);
     if (!d_out) return VGK_ENOMEM;
     P.out = d_out; P.pass = 2;
     if ((rc = be->run_minimizer_seeds_of(P))) return rc;

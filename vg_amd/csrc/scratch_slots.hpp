@@ -1,0 +1,57 @@
+// scratch_slots.hpp — who owns which of the context's cached device buffers (vgk_ctx::scratch, ctx.hpp).  One enumerator per buffer, grouped by
+// the C-ABI file that uses it and numbered by the compiler: a family that needs another buffer adds a name to its group.  Two names share a
+// buffer only through the aliases behind SLOT_COUNT.  "Never aliased": a later call reads what these slots hold through the ctx-> record named.
+#pragma once
+
+enum Slot : int {
+    // ---- banded_api.cpp.  Never aliased: banded_last (vgk_banded_rerun) points into set 0 and BANDED_SCORES.
+    // Two sub-batches in flight: a buffer is BANDED<set>_PROBS + S_*, the file's own index enum (a static_assert there ties the runs to it)
+    BANDED0_PROBS, BANDED0_ORDER, BANDED0_NODES, BANDED0_SEEDS, BANDED0_POOL, BANDED0_STARTS, BANDED0_READS, BANDED0_QUALS, BANDED0_GRAPH, BANDED0_MAT,
+    BANDED0_TB, BANDED0_LAST, BANDED0_OPS, BANDED0_DENSE, BANDED0_RESULTS, BANDED0_END,
+    BANDED1_PROBS = BANDED0_END, BANDED1_ORDER, BANDED1_NODES, BANDED1_SEEDS, BANDED1_POOL, BANDED1_STARTS, BANDED1_READS, BANDED1_QUALS, BANDED1_GRAPH, BANDED1_MAT,
+    BANDED1_TB, BANDED1_LAST, BANDED1_OPS, BANDED1_DENSE, BANDED1_RESULTS, BANDED1_END,
+    BANDED_SCORES = BANDED1_END,       // k-best mode: the full score matrices
+    // the device-geometry path's raw arrays, per sub-batch in flight: BGEOM<set>_PROBS + G_*
+    BGEOM0_PROBS, BGEOM0_NODELEN, BGEOM0_PREDOFF, BGEOM0_PREDIDX, BGEOM0_TMP, BGEOM0_OUT, BGEOM0_END,
+    BGEOM1_PROBS = BGEOM0_END, BGEOM1_NODELEN, BGEOM1_PREDOFF, BGEOM1_PREDIDX, BGEOM1_TMP, BGEOM1_OUT, BGEOM1_END,
+    BKBEST_SUMS = BGEOM1_END, BKBEST_PRES, BKBEST_POPS,      // the k-best walk on the device: what it does not share (BKBEST_* aliases below)
+    // ---- gapless_api.cpp.  Never aliased: ctx->sets (vgk_tail_stage reads the descriptors, the masked reads and the ordered sets here) and
+    // gapless_last (vgk_gapless_rerun).  Both entry points use one name per purpose; the seeded one leaves READS and SEEDS alone.
+    GAPLESS_SCRATCH, GAPLESS_COLD, GAPLESS_PROBS, GAPLESS_READS, GAPLESS_SEEDS, GAPLESS_SORT, GAPLESS_RESULTS, GAPLESS_EXT, GAPLESS_NODES, GAPLESS_MISM,
+    GAPLESS_COUNTERS, GAPLESS_WINNERS, GAPLESS_RETRY, GAPLESS_TAB, GAPLESS_RES_OUT, GAPLESS_EXT_OUT, GAPLESS_NODES_OUT, GAPLESS_READ_OF,
+    // ---- wfa_api.cpp.  Never aliased: ctx->wfa_out (vgk_chain_stitch's LINK pieces read results, paths and edit runs here), wfa_last and
+    // wfa_wave_last (vgk_wfa_rerun).  WFA_RAW, WFA_SRC_OFF: the sequences as the caller holds them, their offsets
+    WFA_SCRATCH, WFA_PROBS, WFA_SEQS, WFA_ORDER, WFA_RESULTS, WFA_PATHS, WFA_EDITS, WFA_COUNTERS,
+    WFA_HANDED_OVER, WFA_SLABS, WFA_DECLINED, WFA_STATS, WFA_PRODUCERS_DONE, WFA_RAW, WFA_SRC_OFF,
+    // ---- gssw_multi_api.cpp (the k-best pinned path; nothing stays for a later call): the matrices' inputs, then the walk on the device
+    MULTI_PROBS, MULTI_READS, MULTI_QUALS, MULTI_GRAPH, MULTI_NODES, MULTI_PREDS, MULTI_MAT, MULTI_CELLS,
+    MULTI_PINNING, MULTI_POOL, MULTI_ORDER, MULTI_RESULTS, MULTI_N_ALIGNMENTS, MULTI_STATUS, MULTI_OPS, MULTI_OPS_OFF, MULTI_OFFS, MULTI_SUMS, MULTI_PRES, MULTI_POPS,
+    // ---- xdrop_band_api.cpp (nothing stays).  Two sub-batches in flight: set 0 is the XBAND0_* aliases below plus these three, set 1 the run
+    // XBAND1_PROBS + D_*, the file's own index enum (a static_assert there ties both sets to it)
+    XBAND0_FMAX, XBAND0_STATS, XBAND0_FRONT,
+    XBAND1_PROBS, XBAND1_READS, XBAND1_QUALS, XBAND1_GRAPH, XBAND1_NODES, XBAND1_PREDS, XBAND1_MAT, XBAND1_CELLS, XBAND1_FMAX, XBAND1_STATS, XBAND1_FRONT,
+    XBAND1_ORDER, XBAND1_RES, XBAND1_OPS, XBAND1_OPSOFF, XBAND1_WANT, XBAND1_OFFS, XBAND1_SUMS, XBAND1_PRES, XBAND1_POPS, XBAND1_END,
+    // ---- tail_api.cpp: the forest's per-call tables (the forest itself is owned by its graph)
+    TAIL_PROBS = XBAND1_END, TAIL_RES, TAIL_COUNTS, TAIL_SCRATCH, TAIL_TMP,
+    // ---- minimizer_api.cpp.  Never aliased: ctx->seeded (vgk_gapless_extend_seeded takes reads, offsets and seeds from the SEEDED_* slots, and
+    // ctx->sets.reads then points there too).  MZLIST_*: vgk_minimizer_list and vgk_minimizer_seeds_of (nothing stays)
+    SEEDED_READS, SEEDED_READ_OFF, SEEDED_TAB, SEEDED_SEEDS,
+    MZLIST_READS, MZLIST_READ_OFF, MZLIST_TAB, MZLIST_ITEMS, MZLIST_MINIMIZERS, MZLIST_TAKE, MZLIST_SEED_TAB, MZLIST_SEEDS,
+    // ---- gssw_wide_api.cpp, chain_api.cpp (nothing stays)
+    WIDE_PROBS, WIDE_ORDER, WIDE_COLINFO, WIDE_PROF, WIDE_NODES, WIDE_PREDS, WIDE_SCRATCH, WIDE_CARRY, WIDE_TB, WIDE_BEST, WIDE_RESULTS, WIDE_OPS,
+    CHAIN_UP, CHAIN_TAB, CHAIN_RES, CHAIN_WORK_M, CHAIN_WORK_E, CHAIN_OUT_M, CHAIN_OUT_E,
+    SLOT_COUNT,                        // sizes vgk_ctx::scratch; only aliases follow
+
+    // ---- deliberate sharing: a second name for a buffer above, so that a context which uses both paths keeps one set of buffers in HBM.
+    // Safe for both: the two calls never overlap under the context lock (vgk_ctx::mu), and neither leaves state behind for a later call.
+    // xdrop set 0 over the k-best pinned path's buffers
+    XBAND0_PROBS = MULTI_PROBS, XBAND0_READS = MULTI_READS, XBAND0_QUALS = MULTI_QUALS, XBAND0_GRAPH = MULTI_GRAPH, XBAND0_NODES = MULTI_NODES,
+    XBAND0_PREDS = MULTI_PREDS, XBAND0_MAT = MULTI_MAT, XBAND0_CELLS = MULTI_CELLS, XBAND0_ORDER = MULTI_OFFS, XBAND0_RES = MULTI_PINNING,
+    XBAND0_OPS = MULTI_POOL, XBAND0_OPSOFF = MULTI_ORDER, XBAND0_WANT = MULTI_RESULTS, XBAND0_OFFS = MULTI_N_ALIGNMENTS, XBAND0_SUMS = MULTI_STATUS,
+    XBAND0_PRES = MULTI_OPS, XBAND0_POPS = MULTI_OPS_OFF,
+    // the banded k-best walk over the gssw k-best walk's buffers
+    BKBEST_POOL = MULTI_PINNING, BKBEST_ORDER = MULTI_POOL, BKBEST_SP_OFF = MULTI_ORDER, BKBEST_SP_LEN = MULTI_RESULTS, BKBEST_PREFIX = MULTI_N_ALIGNMENTS,
+    BKBEST_HOST_ONLY = MULTI_STATUS, BKBEST_RESULTS = MULTI_OPS, BKBEST_N_ALIGNMENTS = MULTI_OPS_OFF, BKBEST_OPS = MULTI_OFFS, BKBEST_OPS_OFF = MULTI_SUMS,
+    BKBEST_STATUS = MULTI_PRES, BKBEST_OFFS = MULTI_POPS,
+};
+constexpr Slot operator+(Slot base, int k) { return (Slot)((int)base + k); }      // a buffer of a run: its first name + the family's index

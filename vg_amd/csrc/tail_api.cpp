@@ -47,8 +47,8 @@ static int tail_forest_core(vgk_ctx* ctx, const vgk_haplo* index, const vgk_tail
     P.index = index->dev; P.n = n;
     const uint32_t per_cu = 512;
     const uint32_t threads = (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max(1, be->compute_units()) * per_cu);
-    uint32_t* d_counts = (uint32_t*)ctx->ensure_scratch(52, sizeof(uint32_t) * 2 * (size_t)(n + 1));
-    TScratch* d_scratch = (TScratch*)ctx->ensure_scratch(53, sizeof(TScratch) * (size_t)std::max(1u, threads));
+    uint32_t* d_counts = (uint32_t*)ctx->ensure_scratch(TAIL_COUNTS, sizeof(uint32_t) * 2 * (size_t)(n + 1));
+    TScratch* d_scratch = (TScratch*)ctx->ensure_scratch(TAIL_SCRATCH, sizeof(TScratch) * (size_t)std::max(1u, threads));
     if (!d_counts || !d_scratch) return VGK_ENOMEM;
     uint32_t* d_first = d_counts + (n + 1);
     int rc = be->zero(d_counts, sizeof(uint32_t) * 2 * (size_t)(n + 1));
@@ -66,7 +66,7 @@ static int tail_forest_core(vgk_ctx* ctx, const vgk_haplo* index, const vgk_tail
     uint32_t* d_slot = (uint32_t*)keep(sizeof(uint32_t) * (N + 1));
     uint32_t* d_owner = owner ? (uint32_t*)keep(sizeof(uint32_t) * (N + 1)) : nullptr;
     // per-call tables of the construction: trim, has_pred, store, slow
-    uint32_t* d_tmp = (uint32_t*)ctx->ensure_scratch(54, sizeof(uint32_t) * 4 * (N + 1));
+    uint32_t* d_tmp = (uint32_t*)ctx->ensure_scratch(TAIL_TMP, sizeof(uint32_t) * 4 * (N + 1));
     if (!d_parent || !d_node || !d_len || !d_col || !d_po || !d_slot || !d_tmp || (owner && !d_owner)) return fail(VGK_ENOMEM);
     uint32_t* d_trim = d_tmp; uint32_t* d_hasp = d_tmp + (N + 1); uint32_t* d_store = d_tmp + 2 * (N + 1); uint32_t* d_slow = d_tmp + 3 * (N + 1);
     rc = be->zero(d_tmp, sizeof(uint32_t) * 4 * (N + 1));
@@ -104,8 +104,8 @@ int vgk_tail_forest(vgk_ctx* ctx, const vgk_haplo* index, const vgk_tail_problem
     *out = nullptr;
     Backend* be = ctx->be.get();
     std::lock_guard<std::mutex> lk(ctx->mu);
-    vgk_tail_problem* d_probs = (vgk_tail_problem*)ctx->ensure_scratch(50, sizeof(vgk_tail_problem) * (size_t)(n + 1));
-    vgk_tail_result* d_res = (vgk_tail_result*)ctx->ensure_scratch(51, sizeof(vgk_tail_result) * (size_t)(n + 1));
+    vgk_tail_problem* d_probs = (vgk_tail_problem*)ctx->ensure_scratch(TAIL_PROBS, sizeof(vgk_tail_problem) * (size_t)(n + 1));
+    vgk_tail_result* d_res = (vgk_tail_result*)ctx->ensure_scratch(TAIL_RES, sizeof(vgk_tail_result) * (size_t)(n + 1));
     if (!d_probs || !d_res) return VGK_ENOMEM;
     int rc = VGK_OK;
     be->watch(0);

@@ -34,7 +34,7 @@ char complement(char c) {
 // The wavefront form's slabs: per resident wavefront the table, its log, the path pool and the backtrace's edit runs, carved out of one
 // allocation per launch size; the table part must be all-zero before a launch (the kernel leaves it so).
 struct WaveSlabs { uint32_t waves, n_slots, max_points, path_cap, mask_width; };
-int carve(vgk_ctx* ctx, WfaHost& H, int slot, const WaveSlabs& z, WwParams& W) {
+int carve(vgk_ctx* ctx, WfaHost& H, Slot slot, const WaveSlabs& z, WwParams& W) {
     Backend* be = ctx->be.get();
     const uint64_t w = z.waves;
     const uint64_t b_slots = 8ull * z.n_slots * w, b_logs = 4ull * z.max_points * w, b_paths = sizeof(WwPath) * (uint64_t)z.path_cap * w, b_runs = 4ull * W_EDITS * w;
@@ -117,15 +117,15 @@ int prepare_wave_form(vgk_ctx* ctx, WfaHost& H, const WfaParams& P, bool after_t
     A.base.max_points_tail = ctx->wfa_point_budget_tail ? ctx->wfa_point_budget_tail : 0xffffffffu;
     if (const char* e = std::getenv("VGAMD_WFA_SMALL_POINTS")) A.small_points = (uint32_t)std::max(16, std::atoi(e));     // (tests: more problems for the large size)
     int rc;
-    if ((rc = carve(ctx, H, 62, z, A))) return rc;
-    char* extra = (char*)ctx->ensure_scratch(63, 64);
+    if ((rc = carve(ctx, H, WFA_SLABS, z, A))) return rc;
+    char* extra = (char*)ctx->ensure_scratch(WFA_DECLINED, 64);
     if (!extra) return VGK_ENOMEM;
     A.todo = P.order; A.n_todo = P.n; A.n_todo_dev = nullptr;
     if (after_threads) { A.todo = P.handed_over; A.n_todo = P.n; A.n_todo_dev = P.n_handed_over; A.base.handed_over = nullptr; }
     A.n_declined = (unsigned long long*)extra;
     A.stats = nullptr;
     if (std::getenv("VGAMD_WFA_STATS")) {                                        // per-problem statistics, printed by the call (a debugging aid)
-        A.stats = (uint32_t*)ctx->ensure_scratch(64, sizeof(uint32_t) * WW_STAT_WORDS * ((size_t)P.n + 1));
+        A.stats = (uint32_t*)ctx->ensure_scratch(WFA_STATS, sizeof(uint32_t) * WW_STAT_WORDS * ((size_t)P.n + 1));
         if (!A.stats || be->zero(A.stats, sizeof(uint32_t) * WW_STAT_WORDS * ((size_t)P.n + 1))) return VGK_ENOMEM;
     }
     ctx->wfa_wave_last[0] = A; ctx->wfa_wave_waves[0] = z.waves;
@@ -273,21 +273,15 @@ int vgk_wfa_extend(vgk_ctx* ctx, const vgk_haplo* index, const vgk_wfa_error_mod
     }
 
     lap(0);                                                                      // descriptors + masked sequences (host threads)
-    int next_slot = 33;
-    auto dev = [&](const void* src, size_t bytes) -> void* {
-        void* d = ctx->ensure_scratch(next_slot++, std::max<size_t>(bytes, 16)); if (!d) return nullptr;
-        if (src && bytes && be->upload(d, src, bytes)) return nullptr;
-        return d;
-    };
-    P.probs = (const WProb*)dev(probs, sizeof(WProb) * n);
-    if (!one_stretch) P.seqs = (const char*)dev(seqs, n_seq + 16);
+    P.probs = ctx->scratch_dev<const WProb>(WFA_PROBS, probs, sizeof(WProb) * n);
+    if (!one_stretch) P.seqs = ctx->scratch_dev<const char>(WFA_SEQS, seqs, n_seq + 16);
     else {
         uint32_t* src_off = H.src_off.get(be, n);
         if (!src_off) return VGK_ENOMEM;
         parallel_for(n, [&](uint32_t i, unsigned) { src_off[i] = probs[i].seq_len ? (uint32_t)((uintptr_t)problems[i].seq - span_lo) : 0u; });
-        char* d_seqs = (char*)ctx->ensure_scratch(next_slot++, n_seq + 16);
-        const char* d_raw = (const char*)ctx->ensure_scratch(66, (uint64_t)(span_hi - span_lo) + 16);
-        const uint32_t* d_src = (const uint32_t*)ctx->ensure_scratch(67, sizeof(uint32_t) * (uint64_t)n);
+        char* d_seqs = (char*)ctx->ensure_scratch(WFA_SEQS, n_seq + 16);
+        const char* d_raw = (const char*)ctx->ensure_scratch(WFA_RAW, (uint64_t)(span_hi - span_lo) + 16);
+        const uint32_t* d_src = (const uint32_t*)ctx->ensure_scratch(WFA_SRC_OFF, sizeof(uint32_t) * (uint64_t)n);
         if (!d_seqs || !d_raw || !d_src || !P.probs) return VGK_ENOMEM;
         if (be->upload((void*)d_raw, (const void*)span_lo, (size_t)(span_hi - span_lo)) || be->upload((void*)d_src, src_off, sizeof(uint32_t) * (size_t)n)) return VGK_ENODEV;
         if (be->zero(d_seqs, 8) || be->zero(d_seqs + 8 + n_seq, 8)) return VGK_ENODEV;
@@ -309,7 +303,7 @@ int vgk_wfa_extend(vgk_ctx* ctx, const vgk_haplo* index, const vgk_wfa_error_mod
     if (mode == 3 && n_graph_nodes <= (1u << 21)) {
         // the default order as ONE stable radix sort on the device: key = length class (longest first, 11 bits) | node (21 bits); the
         // keys are filled on the host threads, the sorted indices never come back (the two host counting sorts cost 5-8 ms per 500 k)
-        uint32_t* d_sort = (uint32_t*)ctx->ensure_scratch(next_slot++, sizeof(uint32_t) * 4 * (size_t)n);       // key, index, sorted key, order
+        uint32_t* d_sort = (uint32_t*)ctx->ensure_scratch(WFA_ORDER, sizeof(uint32_t) * 4 * (size_t)n);       // key, index, sorted key, order
         if (!d_sort) return VGK_ENOMEM;
         std::vector<uint32_t> keys(2 * (size_t)n);
         parallel_for(n, [&](uint32_t i, unsigned) {
@@ -348,7 +342,7 @@ int vgk_wfa_extend(vgk_ctx* ctx, const vgk_haplo* index, const vgk_wfa_error_mod
             order.swap(tmp);
         }
     }
-    P.order = (const uint32_t*)dev(order.data(), sizeof(uint32_t) * n);
+    P.order = ctx->scratch_dev<const uint32_t>(WFA_ORDER, order.data(), sizeof(uint32_t) * n);
     if (P.order && be->sync()) return VGK_ENODEV;                                // (order goes out of scope)
     }
     lap(1);                                                                      // uploads + the hand-out order
@@ -367,20 +361,20 @@ int vgk_wfa_extend(vgk_ctx* ctx, const vgk_haplo* index, const vgk_wfa_error_mod
     if (const char* e = std::getenv("VGAMD_WFA_THREADS_PER_CU")) per_cu = (uint64_t)std::max(64, std::atoi(e));
     const uint32_t threads = wave_form ? 1u : (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max(1, be->compute_units()) * per_cu);
     P.hand_over_points = 0; P.handed_over = nullptr; P.n_handed_over = nullptr;
-    if (wave_form) P.scratch = reinterpret_cast<WScratch*>(ctx->ensure_scratch(32, 64));
+    if (wave_form) P.scratch = reinterpret_cast<WScratch*>(ctx->ensure_scratch(WFA_SCRATCH, 64));
     else
     { const uint64_t want = sizeof(WScratch) * (uint64_t)threads;
-      P.scratch = (WScratch*)ctx->ensure_scratch(32, want);
+      P.scratch = (WScratch*)ctx->ensure_scratch(WFA_SCRATCH, want);
       // the kernel leaves every slab's table all-zero; a fresh (or regrown) allocation is zeroed once
       if (P.scratch && (H.zeroed_ptr != (void*)P.scratch || H.zeroed_bytes < want)) {
-          const uint64_t have = ctx->scratch[32].bytes;
+          const uint64_t have = ctx->scratch[WFA_SCRATCH].bytes;
           if (be->zero(P.scratch, have)) return VGK_ENODEV;
           H.zeroed_ptr = (void*)P.scratch; H.zeroed_bytes = have;
       } }
-    P.results = (vgk_wfa_result*)dev(nullptr, sizeof(vgk_wfa_result) * n);
-    P.paths = (uint32_t*)dev(nullptr, sizeof(uint32_t) * cap_p);
-    P.edits = (uint32_t*)dev(nullptr, sizeof(uint32_t) * cap_e);
-    P.counters = (unsigned long long*)dev(nullptr, 64);
+    P.results = ctx->scratch_dev<vgk_wfa_result>(WFA_RESULTS, nullptr, sizeof(vgk_wfa_result) * n);
+    P.paths = ctx->scratch_dev<uint32_t>(WFA_PATHS, nullptr, sizeof(uint32_t) * cap_p);
+    P.edits = ctx->scratch_dev<uint32_t>(WFA_EDITS, nullptr, sizeof(uint32_t) * cap_e);
+    P.counters = ctx->scratch_dev<unsigned long long>(WFA_COUNTERS, nullptr, 64);
     if (!P.probs || !P.seqs || !P.order || !P.scratch || !P.results || !P.paths || !P.edits || !P.counters) return VGK_ENOMEM;
     int rc;
     if ((rc = be->zero(P.counters, 64))) return rc;
@@ -389,7 +383,7 @@ int vgk_wfa_extend(vgk_ctx* ctx, const vgk_haplo* index, const vgk_wfa_error_mod
     } else if (hybrid) {
         uint32_t hand_over = 16;
         if (const char* e = std::getenv("VGAMD_WFA_HAND_OVER_POINTS")) hand_over = (uint32_t)std::max(8, std::atoi(e));
-        char* extra = (char*)ctx->ensure_scratch(61, sizeof(uint32_t) * ((size_t)n + 8) + 16);
+        char* extra = (char*)ctx->ensure_scratch(WFA_HANDED_OVER, sizeof(uint32_t) * ((size_t)n + 8) + 16);
         if (!extra) return VGK_ENOMEM;
         P.hand_over_points = hand_over; P.n_handed_over = (unsigned long long*)extra; P.handed_over = (uint32_t*)(extra + 16);
         if (be->wfa_concurrent() && std::getenv("VGAMD_WFA_AT_ONCE")) {
@@ -401,7 +395,7 @@ int vgk_wfa_extend(vgk_ctx* ctx, const vgk_haplo* index, const vgk_wfa_error_mod
             uint64_t t_per_cu = 512;
             if (const char* e = std::getenv("VGAMD_WFA_THREADS_PER_CU")) t_per_cu = (uint64_t)std::max(64, std::atoi(e));
             const uint32_t t_threads = (uint32_t)std::min<uint64_t>(n, (uint64_t)std::max(1, be->compute_units()) * t_per_cu);
-            P.producers_done = (uint32_t*)ctx->ensure_scratch(65, 64);
+            P.producers_done = (uint32_t*)ctx->ensure_scratch(WFA_PRODUCERS_DONE, 64);
             if (!P.producers_done) return VGK_ENOMEM;
             ctx->wfa_last = P; ctx->wfa_last_threads = t_threads;
             if ((rc = prepare_wave_form(ctx, H, P, true, 4))) return rc;

@@ -28,11 +28,12 @@ struct BandStage { PinnedBuf<uint8_t> reads, quals, graph, want; PinnedBuf<uint1
                    PinnedBuf<vgk_result> dres; PinnedBuf<vgk_op> dops; PinnedBuf<unsigned long long> stat; };
 struct BandHost { BandStage set[2]; void* ev[2] = {nullptr, nullptr}; Backend* be = nullptr;
                   ~BandHost() { if (be) for (void* e : ev) if (e) be->event_destroy(e); } };
-// device scratch slots of the two sets (ctx.hpp lists who owns which slot)
+// device scratch slots of the two sets (scratch_slots.hpp): set 0 shares the k-best pinned path's buffers, set 1 is the run XBAND1_PROBS + D_*
 enum { D_PROBS, D_READS, D_QUALS, D_GRAPH, D_NODES, D_PREDS, D_MAT, D_CELLS, D_FMAX, D_STATS, D_FRONT, D_ORDER, D_RES, D_OPS, D_OPSOFF, D_WANT, D_OFFS, D_SUMS, D_PRES, D_POPS, D_COUNT };
-constexpr int kSlot[2][D_COUNT] = { {40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 87, 80, 72, 73, 74, 75, 76, 77, 78, 79},
-                                    {100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, 111, 112, 113, 114, 115, 116, 117, 118, 119} };
-static_assert(119 < (int)(sizeof(vgk_ctx::scratch) / sizeof(vgk_ctx::DevBuf)), "scratch slots");
+constexpr Slot kSet0[] = { XBAND0_PROBS, XBAND0_READS, XBAND0_QUALS, XBAND0_GRAPH, XBAND0_NODES, XBAND0_PREDS, XBAND0_MAT, XBAND0_CELLS, XBAND0_FMAX, XBAND0_STATS, XBAND0_FRONT,
+                           XBAND0_ORDER, XBAND0_RES, XBAND0_OPS, XBAND0_OPSOFF, XBAND0_WANT, XBAND0_OFFS, XBAND0_SUMS, XBAND0_PRES, XBAND0_POPS };
+static_assert(sizeof kSet0 / sizeof *kSet0 == D_COUNT && XBAND1_END - XBAND1_PROBS == D_COUNT, "scratch_slots.hpp: XBAND0_* and the XBAND1_* run name D_*");
+inline Slot slot_of(int set, int what) { return set ? XBAND1_PROBS + what : kSet0[what]; }
 
 // one sub-batch of a call between its two halves: packed, uploaded and launched — then fetched and handed out
 struct Sub { uint32_t i = 0, j = 0, m = 0; std::vector<uint32_t> owner; GsswMatrixParams P{}; uint64_t ops_total = 0; bool launched = false; };
@@ -110,7 +111,7 @@ int vgk_xdrop_band_align(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_
 
     // ---- first half of a sub-batch: the problems from `from` on that fit, packed, uploaded, launched
     auto build = [&](uint32_t from, Sub& S, int set) -> int {
-        BandStage& St = Hs.set[set]; const int* slot = kSlot[set];
+        BandStage& St = Hs.set[set];
         uint64_t n_cells = 0, n_read = 0, n_graph = 0, n_nodes = 0, n_preds = 0;
         S.i = from; S.owner.clear(); S.launched = false; S.ops_total = 0;
         // where the sub-batch ends: the running sum of cells and the count decide it (two values per problem)
@@ -183,12 +184,12 @@ int vgk_xdrop_band_align(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_
         lap("pack");
         GsswMatrixParams& P = S.P; P = GsswMatrixParams{};
         P.n = m; P.go = ctx->sc.gap_open; P.ge = ctx->sc.gap_extend;
+        // vgk_ctx::scratch_dev, but for the stream: uploads go on the side stream, under the kernels of the sub-batch before; the launch below waits for them on the device
         auto dev = [&](int what, const void* src, size_t bytes) -> void* {
-            void* d = ctx->ensure_scratch(slot[what], std::max<size_t>(bytes, 16)); if (!d) return nullptr;
-            if (src && bytes && be->upload_side(d, src, bytes)) return nullptr;      // (the side stream: under the kernels of the sub-batch before; the launch below waits for them on the device)
+            void* d = ctx->scratch_dev(slot_of(set, what), nullptr, bytes);
+            if (d && src && bytes && be->upload_side(d, src, bytes)) return nullptr;
             return d;
         };
-        // (set 0's slots are the scratch slots of the k-best pinned path: the two calls never overlap under the context lock)
         P.probs = (MProb*)dev(D_PROBS, probs, sizeof(MProb) * m);
         P.reads = (const uint8_t*)dev(D_READS, reads, n_read); P.quals = qa ? (const uint8_t*)dev(D_QUALS, quals, n_read) : nullptr;
         P.graph = (const uint8_t*)dev(D_GRAPH, graph, n_graph); P.nodes = (const MNode*)dev(D_NODES, nodes, sizeof(MNode) * n_nodes);
@@ -239,7 +240,7 @@ int vgk_xdrop_band_align(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_
 
     // ---- second half: wait for the kernels, pack the ops on the device, bring results and ops back, hand them out in the caller's order
     auto finish = [&](Sub& S, int set) -> int {
-        BandStage& St = Hs.set[set]; const int* slot = kSlot[set];
+        BandStage& St = Hs.set[set];
         const uint32_t m = S.m; const GsswMatrixParams& P = S.P;
         vgk_result* dres = St.dres.get(be, m + 1); vgk_op* dops = nullptr;
         if (!dres) return VGK_ENOMEM;
@@ -247,7 +248,7 @@ int vgk_xdrop_band_align(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_
             int rc;
             if (Hs.ev[set]) { if ((rc = be->fetch_after(Hs.ev[set]))) return rc; }
             else if ((rc = be->sync())) return rc;
-            auto dev = [&](int what, size_t bytes) -> void* { return ctx->ensure_scratch(slot[what], std::max<size_t>(bytes, 16)); };
+            auto dev = [&](int what, size_t bytes) -> void* { return ctx->scratch_dev(slot_of(set, what), nullptr, bytes); };
             const uint32_t blocks = (m + Backend::OPS_SCAN_BLOCK - 1) / Backend::OPS_SCAN_BLOCK;
             uint32_t* offs = (uint32_t*)dev(D_OFFS, sizeof(uint32_t) * m);
             uint32_t* sums = (uint32_t*)dev(D_SUMS, sizeof(uint32_t) * (blocks + 8));
