@@ -1038,6 +1038,16 @@ class Batch:
     def wave_steps(self):
         return self.eng.lib.vgk_batch_wave_steps(self.h)
 
+    def refill_stats(self):
+        """the last speculative run's second fill, read back from the device: dict of `waves` filled a second time, their `steps` summed,
+        `missed` reads, `bounded` (missed reads whose second fill began right of column 0) and `broken` (walks that asked for a code
+        left of where their read's fill began: always 0).  All 0 when the last run did not speculate.  Engine library only."""
+        f = self.eng.lib.vgk_batch_refill_stats
+        f.restype = ctypes.c_int; f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        out = (ctypes.c_uint64 * 5)()
+        self.eng._check(f(self.h, out), "vgk_batch_refill_stats")
+        return dict(zip(("waves", "steps", "missed", "bounded", "broken"), (int(v) for v in out)))
+
     def speculated(self):
         """did the last run fill without traceback codes first (the speculative fill; the context's feedback decides per run)"""
         self.eng.lib.vgk_batch_speculated.argtypes = [ctypes.c_void_p]

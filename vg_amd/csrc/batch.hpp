@@ -1,6 +1,7 @@
 // batch.hpp — a packed gssw batch resident in HBM, shared by the translation units that build one (vgk_api.cpp: per-problem
 // graphs packed on the host; window_api.cpp: windows of a resident graph packed on the device).
 #pragma once
+#include <algorithm>
 #include <cstdlib>
 #include <vector>
 #include "backend.hpp"
@@ -56,6 +57,14 @@ inline int32_t default_tb_mode(int fused, bool near_chain) {
     if (const char* e = std::getenv("VGAMD_TB_CODES")) if (std::atoi(e)) return TB_CODES;
     if (const char* e = std::getenv("VGAMD_TB_REWALK")) if (std::atoi(e)) return TB_REWALK;
     return TB_CODES;
+}
+
+// The second fill of a speculative batch starts each read at refill_col0's column (gssw_device.hpp) unless VGAMD_NO_REFILL_BOUND is set when the
+// batch is packed: then at column 0, as a plain fill does (A/B runs on one library; the way out should a case turn up that the rule does not cover).
+inline void set_refill_bound(GsswParams& P, const vgk_ctx* ctx) {
+    const char* off = std::getenv("VGAMD_NO_REFILL_BOUND");
+    P.refill_bound = (off && std::atoi(off)) || ctx->scale != 8 ? 0 : 1;      // (unscaled scorings run their second fill through the plain fill's kernel, which starts at column 0)
+    P.refill_m = (uint32_t)std::max(0, ctx->max_score) * ctx->scale;
 }
 
 template <class T>

@@ -72,6 +72,9 @@ struct ProbDesc {          // one per read
     uint32_t bonus_start, bonus_end;   // pre-multiplied by the score scale
     uint32_t prof_off;                 // first per-row profile dword in `prof`, or 0xffffffff (profile = prof4[base])
     uint32_t pad;
+    // the second fill of a speculative batch starts this read at column col0 (a multiple of 4; refill_layout_one's rule) instead of 0, with
+    // node0 nodes begun before it; both 0 everywhere else (the packers, refill_restore_one)
+    uint32_t col0, node0;
 };
 
 struct NodeRec {
@@ -125,6 +128,8 @@ struct GsswParams {
     uint32_t refill_wave0, refill_pair0, refill_G, refill_K;
     unsigned long long refill_slot;
     uint32_t* refill_count;
+    int32_t  refill_bound;      // the second fill starts each read where its traceback can first be (refill_col0); 0: at column 0 (VGAMD_NO_REFILL_BOUND)
+    uint32_t refill_m;          // the largest score of a read base against a graph base (quality-adjusted matrices included), scaled, never below 0
     const uint32_t* wave_limit;  // a fill launch over wavefronts whose number only the device knows: wave_begin + *wave_limit is the end
     int32_t  walk_passes;       // 2: the tracebacks run as two kernels — walk_diag_one for every read (whole alignments that are one diagonal run, from the read's and the columns' bytes alone), then walk_one for the reads it left on the miss list; 1: walk_one for all
     int32_t  tb_mode;           // TB_CODES: the fill stores a 4-bit code per cell; TB_REWALK: it stores what the traceback needs to compute them again
@@ -216,7 +221,9 @@ VGK_HD uint32_t ci_word(uint32_t w, uint32_t t, uint32_t R) {
     const uint32_t keep = (1u << (8u * (R - t))) - 1u;                          // (R - t = 1 .. 3 columns left)
     return (w & keep) | (none & ~keep);
 }
-template <int K>
+// SECOND: whether the reads start at their ProbDesc::col0 — 1: yes (the kernel of a speculative batch's second fill), 0: no (every other kernel: nothing
+// of it is compiled into them, the first fill's registers are what they were), -1: where GsswParams::spec_fill says so (the emulator's one fill routine)
+template <int K, int SECOND = -1>
 VGK_HD void lane_init(Lane<K>& s, const GsswParams& P, const WaveDesc& wd, uint32_t lane_id) {
     const uint32_t q = lane_id / wd.G;
     s.g = lane_id - q * wd.G;
@@ -228,11 +235,20 @@ VGK_HD void lane_init(Lane<K>& s, const GsswParams& P, const WaveDesc& wd, uint3
     s.LA = s.LB = 0; s.flagsA = s.flagsB = 0; s.RA = s.RB = 0; s.colA = s.colB = 0;
     s.ciA = s.ciB = s.ciA_n = s.ciB_n = CI_INVALID * 0x01010101u;
     uint32_t roA = 0, roB = 0, poA = 0xffffffffu, poB = 0xffffffffu;
+    uint32_t c0A = 0, c0B = 0, n0A = 0, n0B = 0;      // the second fill of a speculative batch: the reads' first columns and the nodes begun before them
     s.bsA = s.beA = s.bsB = s.beB = 0;
     if (s.probA != 0xffffffffu) { const ProbDesc& d = P.probs[s.probA]; s.LA = d.L; s.flagsA = d.flags; roA = d.read_off; s.RA = d.R; s.colA = d.col_off;
-                                   s.bsA = d.bonus_start; s.beA = d.bonus_end; poA = d.prof_off; }
+                                   s.bsA = d.bonus_start; s.beA = d.bonus_end; poA = d.prof_off; if (SECOND > 0 || (SECOND < 0 && P.spec_fill == 2)) { c0A = d.col0; n0A = d.node0; } }
     if (s.probB != 0xffffffffu) { const ProbDesc& d = P.probs[s.probB]; s.LB = d.L; s.flagsB = d.flags; roB = d.read_off; s.RB = d.R; s.colB = d.col_off;
-                                   s.bsB = d.bonus_start; s.beB = d.bonus_end; poB = d.prof_off; }
+                                   s.bsB = d.bonus_start; s.beB = d.bonus_end; poB = d.prof_off; if (SECOND > 0 || (SECOND < 0 && P.spec_fill == 2)) { c0B = d.col0; n0B = d.node0; } }
+    // (a lane's steps count columns from the read's first one: nothing below knows whether that is column 0)
+    if (SECOND != 0) {
+        s.colA += c0A; s.RA -= c0A; s.colB += c0B; s.RB -= c0B;
+        // (flagsA / flagsB serve lane_best alone, which publishes nothing for a pinned read: nor may it for these — their end cells are the first
+        // fill's, and this fill's columns are not the window's.  The second fill's kernel never gets there; the emulator's routine does.)
+        if (c0A) s.flagsA = VGK_GSSW_PINNED;
+        if (c0B) s.flagsB = VGK_GSSW_PINNED;
+    }
     if (s.g == 0) {   // streams are padded with 8 readable bytes, so these loads never run off the arena
         if (s.probA != 0xffffffffu) s.ciA_n = ci_word(*(const uint32_t*)(P.colinfo + s.colA), 0, s.RA);
         if (s.probB != 0xffffffffu) s.ciB_n = ci_word(*(const uint32_t*)(P.colinfo + s.colB), 0, s.RB);
@@ -248,7 +264,7 @@ VGK_HD void lane_init(Lane<K>& s, const GsswParams& P, const WaveDesc& wd, uint3
     }
     s.out_h = 0; s.out_f = 0; s.info = CI_INVALID2; s.prev_rh = 0;
     s.best_lo = s.best_hi = 0; s.step_lo = s.step_hi = 0;
-    s.nodeA = s.nodeB = 0xffffffffu;
+    s.nodeA = SECOND != 0 ? n0A - 1u : 0xffffffffu; s.nodeB = SECOND != 0 ? n0B - 1u : 0xffffffffu;
     s.one = 0x00010001u;
 }
 
@@ -586,12 +602,14 @@ VGK_HD bool lane_best(const Lane<K>& s, int half, uint32_t& prob, unsigned long 
 #define VGK_WALK_SPEC 8
 #endif
 constexpr uint32_t W_SPEC = VGK_WALK_SPEC;      // diagonal cells fetched together
+constexpr uint32_t W_MISS = 0x100u;            // a code a walker cannot serve (BandWalker: the cell lies outside the recomputed band; Walker: left of ProbDesc::col0)
 struct Walker {
     static constexpr uint32_t SPEC = W_SPEC;
     const GsswParams& P; const ProbDesc& d; uint32_t half, lane0, K; uint64_t tb_off;
     // bit0 = H not from the diagonal, bit1 = H from F (else E), bit2 = next-column E is an extension, bit3 = next-row F is an extension
     VGK_HD uint32_t code(uint32_t r, uint32_t c) const {
-        const uint32_t g = r / K, m = r - g * K, t = c + g, j = m >> 2, i = m & 3u;
+        if (c < d.col0) return W_MISS;                                    // left of where the second fill began (never on a traceback's path: refill_col0)
+        const uint32_t g = r / K, m = r - g * K, t = c - d.col0 + g, j = m >> 2, i = m & 3u;
 #if defined(VGK_WALK_EXP) && VGK_WALK_EXP >= 1      // timing experiments only (results are wrong): the codes come out of a region that stays in L2 (1) / L1 (2, 3)
         const uint32_t w = P.tb[tb_off + (tb_dword(0, t, lane0 + g, (K + 3) >> 2, j) & (VGK_WALK_EXP == 1 ? 0x3ffffu : 0xfffu))];
 #else
@@ -674,7 +692,6 @@ VGK_HD bool walk_end_cell(const GsswParams& P, const ProbDesc& d, unsigned long 
     return have;
 }
 
-constexpr uint32_t W_MISS = 0x100u;            // a code a walker cannot serve (BandWalker: the cell lies outside the recomputed band)
 constexpr int32_t  W_MISSED = 100;             // vgk_result::status of a read whose walk met one: the on-demand traceback takes it (never leaves the engine)
 
 // The traceback proper, over whatever serves the codes: W = Walker (the codes the fill stored), BandWalker (recomputed in a band around the
@@ -808,10 +825,12 @@ VGK_HD int32_t walk_body(const GsswParams& P, uint32_t i, const ProbDesc& d, W& 
     return status;
 }
 
+VGK_HD void tb_bound_broken(const GsswParams& P);
 VGK_HD void walk_one(const GsswParams& P, uint32_t i, unsigned long long best_key) {
     const ProbDesc d = P.probs[i];      // by value: keeps the descriptor in registers across the walk's global stores
     Walker w{P, d, (d.geom >> 16) & 1u, d.lane0, d.geom & 0xffu, P.waves[d.wave].tb_off, 0u, 0xffffffffu, 0u, 0xffffffffu};
-    walk_body(P, i, d, w, best_key);
+    // (a stored-codes walk misses a code only left of col0, where the bound says no traceback goes: counted, and the read keeps W_MISSED as its status)
+    if (walk_body(P, i, d, w, best_key) == W_MISSED) tb_bound_broken(P);
 }
 
 // ---- the first of two passes over a batch of local alignments (GsswParams::walk_passes == 2; round 4) -----------------------------------
@@ -1237,6 +1256,42 @@ VGK_HD void tb_miss_add(const GsswParams& P, uint32_t i) {
 #endif
     tb_miss_list(P)[k] = i;
 }
+// walks that asked for a code left of their read's col0: the upper half of the miss counter's word (zeroed with it before every run)
+VGK_HD uint32_t* tb_bound_broken_count(const GsswParams& P) { return tb_miss_count(P) + 1; }
+VGK_HD void tb_bound_broken(const GsswParams& P) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicAdd(tb_bound_broken_count(P), 1u);
+#else
+    ++*tb_bound_broken_count(P);
+#endif
+}
+// Where the second fill of a read may begin.  A LOCAL read's end cell (r_e, c_e) and score S are the first fill's.  In a CHAIN — every node's only
+// predecessor is the node before it, nothing pinned — a path to the end cell takes at most r_e + 1 diagonal steps, worth at most m each plus the
+// full-length bonuses, and D deleted columns cost at least go + gx (D - 1), gx = min(go, ge); it scores S, so D <= D_max = 1 + floor((m (r_e + 1) +
+// bonuses - S - go) / gx) (0 when the numerator is negative) and the path lies in columns [c_e - r_e - D_max, c_e].  A recurrence begun there with
+// zeros never exceeds the true values and equals them on every co-optimal path, all of which lie inside: every maximum a walk consults has the
+// same winners, so the codes it reads are the full fill's.  Rounded down to a dword of the column stream.  0 — no bound —
+// for gx = 0 and for windows that are no chain, where column indices span more than a path does.  node0 = the nodes begun before that column.
+VGK_HD uint32_t refill_col0(const GsswParams& P, const ProbDesc& d, unsigned long long key, uint32_t& node0) {
+    node0 = 0;
+    const uint32_t S = (uint32_t)(key >> 40), c_e = 0xFFFFFu - (uint32_t)((key >> 20) & 0xFFFFFu), r_e = 0xFFFFFu - (uint32_t)(key & 0xFFFFFu);
+    const uint32_t gx = P.go < P.ge ? P.go : P.ge;
+    if (!S || !gx || r_e >= d.L || c_e >= d.R) return 0;
+    const long long num = (long long)P.refill_m * (r_e + 1u) + d.bonus_start + d.bonus_end - (long long)S * P.scale - P.go;
+    const unsigned long long span = (unsigned long long)r_e + (num < 0 ? 0ull : 1ull + (unsigned long long)num / gx);
+    if (span >= c_e) return 0;
+    const uint32_t col0 = (c_e - (uint32_t)span) & ~3u;
+    if (!col0) return 0;
+    const NodeRec* nodes = P.nodes + d.node_off;
+    uint32_t begun = 0;
+    for (uint32_t n = 0; n < d.n_nodes; ++n) {
+        const NodeRec nr = nodes[n];
+        if (nr.pinning || (n ? nr.n_pred != 1u || P.preds[nr.pred_begin] != n - 1u : nr.n_pred != 0u)) return 0;
+        begun += nr.col_start < col0 ? 1u : 0u;
+    }
+    node0 = begun;
+    return col0;
+}
 // one wavefront of the second fill (GsswParams::spec_fill): the reads at [16 w2 .. ) of the miss list, two to a lane group as in the batch's own
 // wavefronts (vgk_api.cpp / gssw_pack_device.hpp build those); the reads' descriptors learn where their codes will lie
 VGK_HD void refill_layout_one(const GsswParams& P, uint32_t w2) {
@@ -1259,12 +1314,16 @@ VGK_HD void refill_layout_one(const GsswParams& P, uint32_t w2) {
         // a traceback never looks right of its end cell, and a LOCAL alignment's end cell is known (the first fill's best key): the second
         // fill of such a read stops behind that column.  Its own best key is then the maximum over fewer cells — the same cell, first among
         // equals as before — and atomicMax leaves best[] as it is.
+        // Nor does it look left of refill_col0's column: the fill starts there, and the wavefront runs as long as its widest such range.
         uint32_t cols = d.R;
+        d.col0 = 0; d.node0 = 0;
         if ((d.flags & 15u) == (uint32_t)VGK_GSSW_LOCAL) {
-            const uint32_t c_e = 0xFFFFFu - (uint32_t)((P.best[i] >> 20) & 0xFFFFFu);
+            const unsigned long long key = P.best[i];
+            const uint32_t c_e = 0xFFFFFu - (uint32_t)((key >> 20) & 0xFFFFFu);
             if (c_e + 1u < cols) cols = c_e + 1u;
+            if (P.refill_bound && (d.flags & VGK_GSSW_TRACEBACK)) d.col0 = refill_col0(P, d, key, d.node0);
         }
-        rmax = cols > rmax ? cols : rmax;
+        rmax = cols - d.col0 > rmax ? cols - d.col0 : rmax;
         // (where the batch's own fill put the read: kept in the descriptor's spare word, for a later run of this resident batch WITHOUT the
         // speculation — vgk_gssw_run's feedback may decide so — which refill_restore_one hands it back to.  Only the first displacement saves.)
         if (!(d.pad & 0x80000000u)) d.pad = 0x80000000u | (d.wave & 0xffffffu) | ((d.lane0 & 63u) << 24) | (((d.geom >> 16) & 1u) << 30);
@@ -1280,6 +1339,7 @@ VGK_HD void refill_restore_one(const GsswParams& P, uint32_t i) {
     const uint32_t s = d.pad;
     if (!(s & 0x80000000u)) return;
     d.wave = s & 0xffffffu; d.lane0 = (s >> 24) & 63u; d.geom = (d.geom & 0xffffu) | (((s >> 30) & 1u) << 16); d.pad = 0;
+    d.col0 = 0; d.node0 = 0;
 }
 VGK_HD void bandwalk_one(const GsswParams& P, uint32_t i, unsigned long long best_key) {
     const ProbDesc d = P.probs[i];

@@ -165,7 +165,7 @@ VGK_HD void ext_size_one(const WinParams& P, uint32_t i, WinAcc& acc) {
     const uint32_t n1 = P.n + 1;
     ProbDesc d;
     d.col_off = d.R = d.L = d.read_off = d.node_off = d.n_nodes = d.scratch_off = d.n_slots = d.flags = d.ops_off = d.ops_cap = 0;
-    d.max_gap = d.wave = d.lane0 = d.geom = d.Lpad = d.bonus_start = d.bonus_end = d.pad = 0; d.prof_off = 0xffffffffu;
+    d.max_gap = d.wave = d.lane0 = d.geom = d.Lpad = d.bonus_start = d.bonus_end = d.pad = d.col0 = d.node0 = 0; d.prof_off = 0xffffffffu;
     int status = VGK_OK;
     const bool left = x.leftward != 0;
     const uint32_t qlen = left ? x.query_offset : (x.query_offset <= p.read_len ? p.read_len - x.query_offset : 0u);
@@ -250,7 +250,7 @@ VGK_HD void win_size_one(const WinParams& P, uint32_t i, WinAcc& acc) {
     const uint32_t n1 = P.n + 1;
     ProbDesc d;
     d.col_off = d.R = d.L = d.read_off = d.node_off = d.n_nodes = d.scratch_off = d.n_slots = d.flags = d.ops_off = d.ops_cap = 0;
-    d.max_gap = d.wave = d.lane0 = d.geom = d.Lpad = d.bonus_start = d.bonus_end = d.pad = 0; d.prof_off = 0xffffffffu;
+    d.max_gap = d.wave = d.lane0 = d.geom = d.Lpad = d.bonus_start = d.bonus_end = d.pad = d.col0 = d.node0 = 0; d.prof_off = 0xffffffffu;
     int status = VGK_OK;
     const uint32_t mode = p.flags & 15u;
     const bool xdrop = mode == VGK_XDROP_PINNED;

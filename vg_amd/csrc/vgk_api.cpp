@@ -478,6 +478,7 @@ int vgk_gssw_pack(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_t n, ui
     P.dbg = std::getenv("VGAMD_TB_DBG") ? std::atoi(std::getenv("VGAMD_TB_DBG")) : 0; P.tb_mode = default_tb_mode(P.fused, !all.far);
     P.walk_passes = walk2 && !P.fused ? 2 : 1;                          // (local alignments with a traceback: what walk_diag_one serves)
     if (P.walk_passes != 2 || P.tb_mode != TB_CODES) P.spec_fill = 0;
+    set_refill_bound(P, ctx);
     P.key3 = 0;
     if (P.spec_fill) {                                                  // the first fill's column key maximum by v_pk_maximum3_f16 (gssw_device.hpp, K3)
         uint32_t longest = 0; bool xdrop = false;
@@ -757,6 +758,30 @@ uint64_t vgk_batch_alg_bytes(vgk_batch* b) {
 }
 uint64_t vgk_batch_device_bytes(vgk_batch* b) { return b ? b->dev_bytes : 0; }
 uint64_t vgk_batch_wave_steps(vgk_batch* b) { return b ? b->wave_steps : 0; }
+// What the last speculative run's second fill did, read back from the device after the run (engine only, for tests and measurements; not part of
+// include/vgk.h): out[0] = wavefronts filled a second time, [1] = their steps summed, [2] = reads on the miss list, [3] = of those, reads whose
+// second fill began right of column 0 (refill_col0), [4] = walks that asked for a code left of where it began (must be 0).
+extern "C" int vgk_batch_refill_stats(vgk_batch* b, uint64_t out[5]) try {
+    if (!b || !out) return VGK_EINVAL;
+    for (int k = 0; k < 5; ++k) out[k] = 0;
+    { const int rc = vgk_batch_sync(b); if (rc) return rc; }
+    std::lock_guard<std::mutex> lk(b->ctx->mu);
+    if (!b->ran || !b->ran_spec || !b->P.refill_count) return VGK_OK;
+    Backend* be = b->ctx->be.get();
+    uint32_t n_waves2 = 0, counters[2] = {0, 0};
+    int rc = be->download(&n_waves2, b->P.refill_count, sizeof n_waves2);
+    if (!rc) rc = be->download(counters, tb_miss_count(b->P), sizeof counters);
+    if (rc) return rc;
+    const uint32_t missed = std::min(counters[0], b->n);
+    std::vector<WaveDesc> waves(n_waves2); std::vector<uint32_t> list(missed); std::vector<ProbDesc> probs(b->n);
+    if (n_waves2 && (rc = be->download(waves.data(), b->P.waves + b->P.refill_wave0, waves.size() * sizeof(WaveDesc)))) return rc;
+    if (missed && (rc = be->download(list.data(), tb_miss_list(b->P), list.size() * sizeof(uint32_t)))) return rc;
+    if (missed && (rc = be->download(probs.data(), b->P.probs, probs.size() * sizeof(ProbDesc)))) return rc;
+    out[0] = n_waves2; out[2] = missed; out[4] = counters[1];
+    for (const WaveDesc& wd : waves) out[1] += wd.n_steps;
+    for (uint32_t i : list) if (i < b->n && probs[i].col0) ++out[3];
+    return VGK_OK;
+} catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }      // (no exception leaves the C ABI)
 int      vgk_batch_lane(vgk_batch* b) { return b ? b->lane : 0; }
 int      vgk_batch_speculated(vgk_batch* b) { if (!b) return 0; std::lock_guard<std::mutex> lk(b->ctx->mu); return b->ran && b->ran_spec ? 1 : 0; }
 int      vgk_set_speculation(vgk_ctx* ctx, int mode) {

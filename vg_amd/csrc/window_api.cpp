@@ -316,6 +316,7 @@ int vgk_pack_windows_impl(vgk_ctx* ctx, const vgk_dgraph* dg, const char* reads,
     P.fused = 0; P.dbg = std::getenv("VGAMD_TB_DBG") ? std::atoi(std::getenv("VGAMD_TB_DBG")) : 0; P.tb_mode = default_tb_mode(0, near_chain);
     P.walk_passes = walk2 ? 2 : 1;                                    // (windows that were made on the device are tails: X-drop)
     if (P.walk_passes != 2 || P.tb_mode != TB_CODES) P.spec_fill = 0;
+    set_refill_bound(P, ctx);
     P.key3 = 0;
     if (P.spec_fill) {                                                  // (speculation only with the problems at hand on the host: walk2)
         uint32_t longest = 0; bool xdrop = false;
