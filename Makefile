@@ -56,3 +56,9 @@ tests/emu/obj/backend_emu.o: tests/emu/backend_emu.cpp $(LIB_HDRS)
 tests/emu/libvgamd_emu.so: $(EMU_OBJS)
 	$(CXX) -shared -o $@ $(EMU_OBJS) -lpthread
 .PHONY: emu
+
+# test-only: the serial form of find_seeds' choice on the device (minimizer_device.hpp: mz_choose_one) behind one C call
+choose: tests/emu/libvgamd_choose.so
+tests/emu/libvgamd_choose.so: tests/emu/choose_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -shared -o $@ $<
+.PHONY: choose

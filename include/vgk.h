@@ -587,7 +587,8 @@ int  vgk_minimizer_set_policy(vgk_minimizer_index* index, const vgk_seed_policy*
  *                           orientation (minimizer_regions + find, :3918-3965); minimizer_off[n + 1], VGK_EOPS / *written as usual;
  *   vgk_minimizer_seeds_of  the seeds of the minimizers the caller TAKES (take[j] != 0), one per hit in index order (key, node, offset), nothing
  *                           de-duplicated (:4290-4340: one Seed per hit): seed_off[n_minimizers + 1] = where minimizer j's seeds start.
- * A seed is (oriented node, read offset - node offset) on the strand the read reads forward on, as above. */
+ * A seed is (oriented node, read offset - node offset) on the strand the read reads forward on, as above.
+ * The engine library also makes that choice on the device, and all three steps in one call: include/vgk_engine.h. */
 typedef struct vgk_read_minimizer { uint64_t key; uint32_t offset, hits, flags, reserved; } vgk_read_minimizer;
 #define VGK_MINIMIZER_REVERSE 1u       /* flags: the canonical k-mer is the reverse complement of the read's */
 int  vgk_minimizer_list(vgk_ctx* ctx, const vgk_minimizer_index* index, const char* reads, const uint64_t* read_off, uint32_t n,

@@ -1,0 +1,78 @@
+/*
+ * vgk_engine.h — entry points of the ENGINE library (vg_amd/libvgamd.so) that the CPU oracle has no counterpart for.
+ *
+ * include/vgk.h is the ABI both libraries export, symbol for symbol; what is declared here exists in the engine library only: calls whose
+ * reference is not the oracle but a restatement elsewhere in the tree, and counters of the engine's own machinery.  Types, error codes and
+ * conventions are vgk.h's (return 0 = VGK_OK, < 0 = VGK_E*; plain pointers and sizes; no exception crosses the boundary); vgk_abi_version()
+ * is not touched by additions here.
+ *
+ * ---- find_seeds' choice on the device, for reads of any length ---------------------------------------------------------------------------
+ * vgk.h's vgk_minimizer_list / vgk_minimizer_seeds_of leave MinimizerMapper::find_seeds' choice of minimizers (src/minimizer_mapper.cpp:4109-4440)
+ * to the caller between them.  The two calls below make it on the device, by exactly the rule of the host shim's select_minimizers
+ * (vg_amd/host/seed_policy.cpp:55-193), for any number of minimizers per read: find_minimizers' scores (1 + ln(hard_hit_cap) - ln(hits), 1 beyond
+ * the hard cap, 0 without hits — the logarithms taken once on the host), the order (score descending, key, read position), the runs that share the
+ * best score shuffled as sort_shuffling_ties shuffles them (Knuth's shuffle over std::minstd_rand seeded from the read's bytes — THE BYTES THE CALLER
+ * GIVES: lower case and N included, nothing is masked, and no read is ever handed back to the host), window downsampling (sample_minimal), and
+ * the filters in score order, run by run: downsampled, no hits, the run's hits beyond the hard cap, exclude-overlapping, the unique-minimizer
+ * budget (max_unique_min / num_bp_per_min / minimizer_coverage_flank), the score fraction.  Single-end rule: one generator per read.
+ *
+ * A C caller that maps long reads needs nothing but
+ *     vgk_create -> vgk_minimizer_index_create -> vgk_minimizer_find_seeds (sizes unknown: call with cap_m = cap_s = 0, read written[0..1] off
+ *     VGK_EOPS, allocate, call again)
+ * and gets, per read, its minimizers, which of them were taken, and the seeds of those.
+ */
+#ifndef VGK_ENGINE_H
+#define VGK_ENGINE_H
+#include "vgk.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* MinimizerMapper's fields of the same names (src/minimizer_mapper.hpp:140-260).  0 switches off: hit_cap (with minimizer_score_fraction 1.0:
+ * the score filter), max_unique_min (the budget), num_bp_per_min (its read-length term), exclude_overlapping_min, minimizer_downsampling_window_count.
+ * The downsampling window of a read of L bases is min(L / window_count, max_window_length), none when L < window_count * k. */
+typedef struct vgk_find_seeds_policy {
+    uint32_t hit_cap, hard_hit_cap;  double minimizer_score_fraction;
+    uint32_t max_unique_min, num_bp_per_min, minimizer_coverage_flank, exclude_overlapping_min;
+    uint32_t minimizer_downsampling_window_count, reserved;  uint64_t minimizer_downsampling_max_window_length;
+} vgk_find_seeds_policy;
+
+/* The filter that dropped a minimizer (SeedFilter of vg_amd/host/seed_policy.hpp); 0 = its hits become seeds */
+#define VGK_SEED_TAKEN        0
+#define VGK_SEED_DOWNSAMPLED  1
+#define VGK_SEED_NO_HITS      2
+#define VGK_SEED_HARD_HIT_CAP 3
+#define VGK_SEED_OVERLAPPING  4
+#define VGK_SEED_MAX_MIN      5
+#define VGK_SEED_HIT_CAP      6
+
+/* The choice alone, over a list as vgk_minimizer_list answers it — any list: no index is needed.  Read r is reads[read_off[r] .. read_off[r + 1]),
+ * its minimizers are minimizers[minimizer_off[r] .. minimizer_off[r + 1]) in order of read offset, each k bases long (key, offset, hits are read;
+ * flags are not).  verdict[j] (one byte per minimizer): VGK_SEED_*.
+ * VGK_EINVAL: hard_hit_cap 0 or above 65535; a fraction outside [0, 1]; a minimizer that does not fit its read (offset + k > read length) or
+ * lies before its predecessor; a read whose downsampling window is shorter than k (the reference stops there). */
+int vgk_minimizer_choose(vgk_ctx* ctx, const vgk_find_seeds_policy* policy, uint32_t k, const char* reads, const uint64_t* read_off, uint32_t n,
+                         const uint64_t* minimizer_off, const vgk_read_minimizer* minimizers, uint8_t* verdict);
+
+/* List -> choice -> the seeds of the taken, in one call: the list and the choice stay in HBM between the three groups of kernels.  Outputs as
+ * those of vgk_minimizer_list, the caller's choice and vgk_minimizer_seeds_of: minimizer_off[n + 1]; minimizers and take (1 = taken) up to cap_m;
+ * seed_off[n_minimizers + 1] (room for cap_m + 1) and seeds up to cap_s.  VGK_EOPS when cap_m or cap_s is too small, with written[0] = the
+ * minimizers and written[1] = the seeds there are — both from one call, whichever was short: the list is made in HBM whatever room the caller has. */
+int vgk_minimizer_find_seeds(vgk_ctx* ctx, const vgk_minimizer_index* index, const vgk_find_seeds_policy* policy, const char* reads, const uint64_t* read_off, uint32_t n,
+                             uint64_t* minimizer_off, vgk_read_minimizer* minimizers, uint8_t* take, size_t cap_m,
+                             uint64_t* seed_off, vgk_seed* seeds, size_t cap_s, size_t written[2]);
+
+/* Device time (ms) of the choice kernels of the last vgk_minimizer_choose / vgk_minimizer_find_seeds call on this context */
+double vgk_minimizer_choose_last_ms(vgk_ctx* ctx);
+
+/* ---- the speculative fill's counters ------------------------------------------------------------------------------------------------------
+ * What the second fill of the last speculative run of a resident gssw batch did, read back from the device after the run (for tests and
+ * measurements): out[0] = wavefronts filled a second time, out[1] = their steps summed, out[2] = reads on the miss list, out[3] = of those, reads
+ * whose second fill began right of column 0, out[4] = walks that asked for a code left of where it began (must be 0).  All 0 when the last run
+ * did not speculate ("speculation with feedback"). */
+int vgk_batch_refill_stats(vgk_batch* batch, uint64_t out[5]);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

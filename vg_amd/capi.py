@@ -65,6 +65,19 @@ WFA_MATCH, WFA_MISMATCH, WFA_INSERTION, WFA_DELETION = 0, 1, 2, 3
 WFA_NO_NODE = 0xffffffff
 WFA_DEFAULT_MODEL = ((0.03, 1, 6), (0.05, 1, 10), (0.1, 1, 20), (0.1, 10, 200))      # gbwt_extender.hpp:386-395
 READ_MINIMIZER_DT = np.dtype([("key", "<u8"), ("offset", "<u4"), ("hits", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])      # vgk_read_minimizer
+
+
+class FindSeedsPolicy(ctypes.Structure):       # vgk_find_seeds_policy (include/vgk_engine.h)
+    _fields_ = [("hit_cap", ctypes.c_uint32), ("hard_hit_cap", ctypes.c_uint32), ("minimizer_score_fraction", ctypes.c_double),
+                ("max_unique_min", ctypes.c_uint32), ("num_bp_per_min", ctypes.c_uint32), ("minimizer_coverage_flank", ctypes.c_uint32), ("exclude_overlapping_min", ctypes.c_uint32),
+                ("minimizer_downsampling_window_count", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("minimizer_downsampling_max_window_length", ctypes.c_uint64)]
+
+
+def find_seeds_policy(P):
+    """a policy in the keys of pipeline.GIRAFFE_LONG_READ_POLICY -> FindSeedsPolicy"""
+    return FindSeedsPolicy(int(P["hit_cap"]), int(P["hard_hit_cap"]), float(P["score_fraction"]), int(P["max_unique_min"]), int(P["num_bp_per_min"]), int(P["coverage_flank"]),
+                           int(bool(P["exclude_overlapping_min"])), int(P["window_count"]), 0, min(int(P["max_window_length"]), (1 << 64) - 1))
+
 MINIMIZER_REVERSE = 1
 # vgk_chain_stitch (include/vgk.h): pieces of a read's chain in, one composed alignment per read out
 CHAIN_PIECE_DT = np.dtype([("kind", "<u4"), ("link", "<u4"), ("node_offset", "<u4"), ("path_begin", "<u4"), ("path_len", "<u4"), ("edit_begin", "<u4"), ("n_edits", "<u4"), ("reserved", "<u4")])
@@ -573,6 +586,45 @@ class Engine:
         seeds = np.zeros(cap, dtype=SEED_DT)
         self._check(self.lib.vgk_minimizer_seeds_of(self.h, mindex.h, recs.ctypes.data, take.ctypes.data, len(recs), soff.ctypes.data, seeds.ctypes.data, cap, ctypes.byref(written)), "vgk_minimizer_seeds_of")
         return soff, seeds[:written.value]
+
+    def minimizer_choose(self, policy, k, reads, read_off, minimizer_off, minimizers):
+        """vgk_minimizer_choose (include/vgk_engine.h): find_seeds' choice on the device over a list as minimizer_list answers it (any list: no index).
+        policy: the keys of pipeline.GIRAFFE_LONG_READ_POLICY -> verdict per minimizer, uint8 (0 = taken, otherwise the SEED_* filter that dropped it)"""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8); off = np.ascontiguousarray(read_off, dtype=np.uint64); moff = np.ascontiguousarray(minimizer_off, dtype=np.uint64)
+        recs = np.ascontiguousarray(minimizers, dtype=READ_MINIMIZER_DT); pol = find_seeds_policy(policy)
+        verdict = np.zeros(max(len(recs), 1), dtype=np.uint8)
+        self.lib.vgk_minimizer_choose.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_minimizer_choose(self.h, ctypes.byref(pol), k, reads.ctypes.data if len(reads) else None, off.ctypes.data, len(off) - 1, moff.ctypes.data,
+                                                  recs.ctypes.data if len(recs) else None, verdict.ctypes.data), "vgk_minimizer_choose")
+        return verdict[:len(recs)]
+
+    def minimizer_find_seeds(self, mindex, policy, reads, read_off, cap_m=None, cap_s=None):
+        """vgk_minimizer_find_seeds (include/vgk_engine.h): list -> find_seeds' choice -> the seeds of the taken, all on the device, one call.
+        -> (minimizer_off [n + 1] uint64, records READ_MINIMIZER_DT, take uint8, seed_off [len(records) + 1] uint64, seeds SEED_DT).
+        cap_m / cap_s: room to offer at first (default: a guess); too little costs a second call with the sizes the first one answered"""
+        reads = np.ascontiguousarray(reads, dtype=np.uint8); off = np.ascontiguousarray(read_off, dtype=np.uint64); n = len(off) - 1
+        pol = find_seeds_policy(policy)
+        moff = np.zeros(n + 1, dtype=np.uint64); written = (ctypes.c_size_t * 2)()
+        f = self.lib.vgk_minimizer_find_seeds
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        cap_m = max(16, int(len(reads)) // 4) if cap_m is None else int(cap_m); cap_s = 4 * cap_m if cap_s is None else int(cap_s)
+        self.find_seeds_calls = 0
+        for attempt in range(2):
+            recs = np.zeros(max(cap_m, 1), dtype=READ_MINIMIZER_DT); take = np.zeros(max(cap_m, 1), dtype=np.uint8); soff = np.zeros(cap_m + 1, dtype=np.uint64); seeds = np.zeros(max(cap_s, 1), dtype=SEED_DT)
+            rc = f(self.h, mindex.h, ctypes.byref(pol), reads.ctypes.data if len(reads) else None, off.ctypes.data, n, moff.ctypes.data, recs.ctypes.data, take.ctypes.data, cap_m,
+                   soff.ctypes.data, seeds.ctypes.data, cap_s, written)
+            self.find_seeds_calls += 1
+            if rc != VGK_EOPS:
+                break
+            cap_m = max(cap_m, int(written[0])); cap_s = max(cap_s, int(written[1]))
+        self._check(rc, "vgk_minimizer_find_seeds")
+        m = int(written[0])
+        return moff, recs[:m], take[:m], soff[:m + 1], seeds[:int(written[1])]
+
+    def minimizer_choose_last_ms(self):
+        self.lib.vgk_minimizer_choose_last_ms.restype = ctypes.c_double; self.lib.vgk_minimizer_choose_last_ms.argtypes = [ctypes.c_void_p]
+        return self.lib.vgk_minimizer_choose_last_ms(self.h)
 
     def minimizer_last_ms(self):
         self.lib.vgk_minimizer_last_ms.restype = ctypes.c_double; self.lib.vgk_minimizer_last_ms.argtypes = [ctypes.c_void_p]

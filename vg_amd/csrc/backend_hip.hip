@@ -825,6 +825,207 @@ __global__ void __launch_bounds__(256) rescue_requests_kernel(const RqParams P, 
 // ---- seeding reads of any length (minimizer_device.hpp): a lane per read lists its minimizers, a lane per minimizer writes its seeds
 __global__ void __launch_bounds__(64) minimizer_list_kernel(const MzListParams P) { mz_list_one(P, blockIdx.x * 64 + threadIdx.x); }
 __global__ void __launch_bounds__(256) minimizer_seeds_of_kernel(const MzSeedsOfParams P) { mz_seeds_of_one(P, blockIdx.x * 256 + threadIdx.x); }
+
+// ---- find_seeds' whole choice for reads of any length (minimizer_device.hpp: mz_choose_one is the rule and the checker): one wavefront per read.
+// Cooperative: loading and ranking the list, the bitonic sort of (rank, key, position), the run boundaries, laying the shuffled runs out, the
+// runs' hit sums, and every range operation on the two coverage bitmaps (a 64-bit word per lane, the "any bit set" test one ballot).  In one
+// order, carried out by all lanes alike over uniform values (no divergence, nothing to hand from lane to lane): the downsampling sweep, Knuth's
+// shuffle of the top runs, the sum of the base target and the filter pass, whose 64 next minimizers sit one in each lane's registers.
+// The work arrays are LDS (ChooseLds: 13-bit positions, 16-bit indices) or a slab in HBM per workgroup (ChooseSlab), same code.
+struct ChooseLds  { using ORD = uint32_t; using IDX = uint16_t; static constexpr uint32_t BITS = 13; };
+struct ChooseSlab { using ORD = uint64_t; using IDX = uint32_t; static constexpr uint32_t BITS = 32; };
+template <class T> struct ChooseWork {
+    uint64_t* key; typename T::ORD* ord;          // the sort's records: key | rank << BITS | position (top bit: kept by the downsampling); afterwards ord = position | FLAG (first of its run) | KEPT
+    typename T::ORD* tmp;                         // the shuffled top runs laid out
+    uint32_t* hits; uint32_t* run_hits;           // in the final order: a minimizer's hits; at a run's first minimizer the run's
+    typename T::IDX* start; typename T::IDX* perm; // the top runs: where each starts, their permutation
+    typename T::IDX* off; typename T::IDX* dq;    // the downsampling sweep: read offsets in read order, its line
+    uint64_t* cov; uint64_t* ovl;                 // covered (flanked), covered_by_minimizer
+};
+__device__ inline uint32_t choose_bc(uint32_t v, uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j); }
+__device__ inline double choose_bc(double v, uint32_t j) { const uint64_t u = (uint64_t)__double_as_longlong(v); return __longlong_as_double((long long)(((uint64_t)choose_bc((uint32_t)(u >> 32), j) << 32) | choose_bc((uint32_t)u, j))); }
+__device__ inline uint64_t choose_word_mask(uint64_t w, uint64_t lo, uint64_t hi) {      // the bits of word w inside [lo, hi), hi > lo, w in [lo >> 6, (hi - 1) >> 6]
+    uint64_t mask = ~0ull;
+    if (w == (lo >> 6)) mask &= ~0ull << (lo & 63);
+    if (w == ((hi - 1) >> 6)) mask &= ~0ull >> (63 - ((hi - 1) & 63));
+    return mask;
+}
+__device__ inline void choose_mark(uint64_t* bm, uint64_t lo, uint64_t hi, uint32_t lane) {
+    if (lo < hi) for (uint64_t w = (lo >> 6) + lane; w <= ((hi - 1) >> 6); w += 64) bm[w] |= choose_word_mask(w, lo, hi);
+    __syncthreads();
+}
+__device__ inline bool choose_any(const uint64_t* bm, uint64_t lo, uint64_t hi, uint32_t lane) {
+    bool hit = false;
+    if (lo < hi) for (uint64_t w = (lo >> 6) + lane; w <= ((hi - 1) >> 6); w += 64) hit = hit || (bm[w] & choose_word_mask(w, lo, hi)) != 0;
+    return __ballot(hit) != 0;
+}
+__device__ inline uint32_t choose_seed(const char* seq, uint64_t L, uint32_t lane) {      // seed = seed * 13 + byte over the read: a stretch per lane, then the stretches in order
+    const uint64_t chunk = (L + 63) / 64, lo = lane * chunk < L ? lane * chunk : L, hi = lo + chunk < L ? lo + chunk : L;
+    uint32_t part = 0, pw = 1;
+    for (uint64_t i = lo; i < hi; ++i) { part = part * 13u + (uint32_t)(uint8_t)seq[i]; pw *= 13u; }
+    uint32_t s = 0;
+    for (uint32_t j = 0; j < 64; ++j) s = s * choose_bc(pw, j) + choose_bc(part, j);
+    return s;
+}
+template <class T> __device__ void choose_read(const MzChooseParams& P, uint32_t r, const ChooseWork<T>& W, uint32_t lane) {
+    using ORD = typename T::ORD; using IDX = typename T::IDX;
+    constexpr uint32_t TOP = sizeof(ORD) * 8 - 1, BITS = T::BITS;
+    constexpr ORD FLAG = (ORD)1 << TOP, KEPT = (ORD)1 << (TOP - 1), IMASK = ((ORD)1 << BITS) - 1;
+    const MzChoosePolicy& Q = P.policy;
+    const uint64_t a = P.min_off[r]; const uint32_t n = (uint32_t)(P.min_off[r + 1] - a);
+    if (!n) return;
+    const vgk_read_minimizer* m = P.mins + a; uint8_t* out = P.verdict + a;
+    const char* seq = P.reads + P.read_off[r]; const uint64_t L = P.read_off[r + 1] - P.read_off[r]; const uint32_t k = P.k;
+    uint32_t np = 1; while (np < n) np <<= 1;
+    for (uint32_t i = lane; i < np; i += 64) {
+        if (i < n) { const vgk_read_minimizer rec = m[i]; W.key[i] = rec.key; W.ord[i] = ((ORD)mz_choose_rank(Q, rec.hits) << BITS) | (ORD)i; W.off[i] = (IDX)rec.offset; }
+        else { W.key[i] = ~0ull; W.ord[i] = (ORD)~FLAG; }
+    }
+    __syncthreads();
+    // ---- window downsampling, in read order (what it keeps: the records' top bit)
+    bool downsampling = false;
+    const uint64_t window = mz_choose_window(Q, L, k);
+    if (window) {
+        const uint32_t nohit = 2u * Q.hard_hit_cap + 2u;
+        mz_sample_minimal(n, k, window, L, W.dq, [&](uint32_t i) { return (uint64_t)W.off[i]; },
+            [&](uint32_t x, uint32_t y) { const uint32_t px = (uint32_t)((W.ord[x] & ~FLAG) >> BITS), py = (uint32_t)((W.ord[y] & ~FLAG) >> BITS);
+                                          return px != nohit && (px < py || (px == py && W.key[x] < W.key[y])); },
+            [&](uint32_t i) { W.ord[i] |= FLAG; downsampling = true; });
+        __syncthreads();
+    }
+    // ---- the order: a bitonic sort of the records, ascending (rank, key, position); the padding sorts last
+    for (uint32_t kk = 2; kk <= np; kk <<= 1) for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
+        for (uint32_t t = lane; t < np / 2; t += 64) {
+            const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i | j;
+            const ORD oi = W.ord[i], ol = W.ord[l]; const uint64_t ki = W.key[i], kl = W.key[l];
+            const ORD ri = (oi & ~FLAG) >> BITS, rl = (ol & ~FLAG) >> BITS;
+            const bool l_first = rl < ri || (rl == ri && (kl < ki || (kl == ki && (ol & IMASK) < (oi & IMASK))));
+            if (l_first == ((i & kk) == 0)) { W.ord[i] = ol; W.ord[l] = oi; W.key[i] = kl; W.key[l] = ki; }
+        }
+        __syncthreads();
+    }
+    // ---- the runs (first of its key: FLAG) and the top tie: `elements` minimizers in `runs` runs, as the shim counts them
+    const uint32_t rank0 = (uint32_t)((W.ord[0] & ~FLAG) >> BITS);
+    __syncthreads();
+    uint32_t elements = 0, runs = 0;
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t pos = base + lane; const bool valid = pos < n;
+        const ORD o = valid ? W.ord[pos] : (ORD)0;
+        const bool first = valid && (pos == 0 || W.key[pos] != W.key[pos - 1]), top = valid && (uint32_t)((o & ~FLAG) >> BITS) == rank0;
+        if (valid) W.ord[pos] = (o & IMASK) | (first ? FLAG : (ORD)0) | ((o & FLAG) ? KEPT : (ORD)0);
+        elements += (uint32_t)__popcll(__ballot(top)); runs += (uint32_t)__popcll(__ballot(top && first));
+    }
+    __syncthreads();
+    while (elements < n && !(W.ord[elements] & FLAG)) ++elements;             // (the last top run ends where its key ends)
+    if (runs >= 2u) {
+        uint32_t found = 0;
+        for (uint32_t base = 0; base < elements; base += 64) {
+            const uint32_t pos = base + lane; const bool f = pos < elements && (W.ord[pos] & FLAG) != 0;
+            const uint64_t b = __ballot(f);
+            if (f) W.start[found + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = (IDX)pos;
+            found += (uint32_t)__popcll(b);
+        }
+        for (uint32_t i = lane; i < runs; i += 64) W.perm[i] = (IDX)i;
+        const uint32_t seed = choose_seed(seq, L, lane);
+        __syncthreads();
+        uint32_t x = mz_minstd_first(seed);
+        for (uint32_t i = 1; i < runs; ++i) { x = mz_minstd_next(x); const uint32_t j = x % (i + 1u); const IDX t = W.perm[j]; W.perm[j] = W.perm[i]; W.perm[i] = t; }
+        __syncthreads();
+        uint32_t carry = 0;
+        for (uint32_t base = 0; base < runs; base += 64) {
+            const uint32_t i = base + lane; uint32_t s = 0, len = 0;
+            if (i < runs) { const uint32_t q = W.perm[i]; s = W.start[q]; len = (q + 1u < runs ? (uint32_t)W.start[q + 1u] : elements) - s; }
+            uint32_t inc = len;
+            for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(inc, d); if (lane >= d) inc += v; }
+            const uint32_t dst = carry + inc - len;
+            for (uint32_t t = 0; t < len; ++t) W.tmp[dst + t] = W.ord[s + t];
+            carry += choose_bc(inc, 63);
+        }
+        __syncthreads();
+        for (uint32_t q = lane; q < elements; q += 64) W.ord[q] = W.tmp[q];
+        __syncthreads();
+    }
+    // ---- hits in the final order, the runs' sums, clean bitmaps
+    for (uint32_t q = lane; q < n; q += 64) W.hits[q] = m[(uint32_t)(W.ord[q] & IMASK)].hits;
+    for (uint64_t w = lane; w < (L + 64) / 64; w += 64) { W.cov[w] = 0; W.ovl[w] = 0; }
+    __syncthreads();
+    for (uint32_t q = lane; q < n; q += 64) if (W.ord[q] & FLAG) {
+        uint64_t s = 0; uint32_t e = q;
+        do { s += W.hits[e]; ++e; } while (e < n && !(W.ord[e] & FLAG));
+        W.run_hits[q] = s > 0xffffffffull ? 0xffffffffu : (uint32_t)s;
+    }
+    __syncthreads();
+    const bool score_filter = Q.hit_cap != 0 || Q.fraction != 1.0;
+    double target = 0.0, selected = 0.0;
+    if (score_filter) {
+        double sum = 0.0;
+        for (uint32_t base = 0; base < n; base += 64) {
+            const double sc = base + lane < n ? mz_choose_score(Q, W.hits[base + lane]) : 0.0;
+            const uint32_t cnt = n - base < 64u ? n - base : 64u;
+            for (uint32_t j = 0; j < cnt; ++j) sum = mz_add(sum, choose_bc(sc, j));
+        }
+        target = mz_add(mz_mul(sum, Q.fraction), 0.000001);
+    }
+    // ---- the filters, in score order, run by run
+    const uint64_t by_read_length = Q.num_bp_per_min ? L / Q.num_bp_per_min : 0, budget = Q.max_unique_min > by_read_length ? Q.max_unique_min : by_read_length;
+    uint64_t taken = 0; uint32_t worst_kept_hits = 0, run_hits = 0; bool taking_run = false;
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t pos = base + lane; const bool valid = pos < n;
+        const ORD o = valid ? W.ord[pos] : (ORD)0; const uint32_t idx = (uint32_t)(o & IMASK);
+        const uint32_t my_hits = valid ? W.hits[pos] : 0u, my_run = valid && (o & FLAG) ? W.run_hits[pos] : 0u, my_off = valid ? m[idx].offset : 0u;
+        const uint32_t my_flags = ((o & FLAG) ? 1u : 0u) | ((o & KEPT) ? 2u : 0u);
+        const double my_score = mz_choose_score(Q, my_hits);
+        uint32_t my_verdict = 0;
+        const uint32_t cnt = n - base < 64u ? n - base : 64u;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint32_t hits = choose_bc(my_hits, j), flags = choose_bc(my_flags, j); const uint64_t off = choose_bc(my_off, j);
+            if (flags & 1u) { run_hits = choose_bc(my_run, j); taking_run = false; }
+            uint32_t failed = MZ_TAKEN;
+            if (downsampling && !(flags & 2u)) failed = MZ_DOWNSAMPLED;
+            else if (!hits) failed = MZ_NO_HITS;
+            else if (run_hits > Q.hard_hit_cap) failed = MZ_HARD_HIT_CAP;
+            if (!failed && Q.exclude_overlapping) {
+                const uint64_t e = off + k < L ? off + k : L, stop = off + k < L + 1 ? off + k : L + 1;
+                if (((W.ovl[off >> 6] >> (off & 63)) & 1ull) || ((W.ovl[e >> 6] >> (e & 63)) & 1ull)) failed = MZ_OVERLAPPING;
+                else choose_mark(W.ovl, off, stop, lane);
+            }
+            if (!failed && Q.max_unique_min != 0) {
+                const uint64_t lo = off < Q.flank ? 0 : off - Q.flank, hi = off + k + Q.flank < L ? off + k + Q.flank : L;
+                if (taken < budget) { choose_mark(W.cov, lo, hi, lane); if (hits > worst_kept_hits) worst_kept_hits = hits; }
+                else if (hits > worst_kept_hits) failed = MZ_MAX_MIN;
+                else if (choose_any(W.cov, lo, hi, lane)) failed = MZ_MAX_MIN;
+                else choose_mark(W.cov, lo, hi, lane);
+            }
+            if (!failed && score_filter) {
+                const double sc = choose_bc(my_score, j);
+                if (hits <= Q.hit_cap || mz_add(selected, sc) <= target || taking_run) selected = mz_add(selected, sc);
+                else { failed = MZ_HIT_CAP; target = selected; }
+            }
+            if (lane == j) my_verdict = failed;
+            if (!failed) { taking_run = true; ++taken; }
+        }
+        if (valid) out[idx] = (uint8_t)(P.as_take ? (my_verdict ? 0u : 1u) : my_verdict);
+    }
+}
+__global__ void __launch_bounds__(64) minimizer_choose_kernel(const MzChooseParams P) {
+    __shared__ uint64_t key[MZ_CHOOSE_LDS_MAX];
+    __shared__ uint32_t ord[MZ_CHOOSE_LDS_MAX];
+    __shared__ uint16_t dq[MZ_CHOOSE_LDS_MAX];
+    __shared__ uint64_t bits[MZ_CHOOSE_LDS_MAX / 4];      // before the sort the read offsets (16 bits each), after it the two bitmaps of MZ_CHOOSE_LDS_BASES + 1 bits
+    static_assert((MZ_CHOOSE_LDS_BASES + 1) * 2 <= MZ_CHOOSE_LDS_MAX / 4 * 64 && MZ_CHOOSE_LDS_MAX <= (1u << ChooseLds::BITS) && MZ_CHOOSE_LDS_BASES < 65536, "the LDS layout of the choice");
+    ChooseWork<ChooseLds> W;
+    // once sorted, the records need their keys no longer: the keys' 32 KiB then hold the layout / the hits (16 KiB) and the top runs' tables / the runs' sums (16 KiB)
+    W.key = key; W.ord = ord; W.tmp = (uint32_t*)key; W.hits = (uint32_t*)key; W.start = (uint16_t*)(key + MZ_CHOOSE_LDS_MAX / 2); W.perm = (uint16_t*)(key + MZ_CHOOSE_LDS_MAX / 4 * 3);
+    W.run_hits = (uint32_t*)(key + MZ_CHOOSE_LDS_MAX / 2); W.off = (uint16_t*)bits; W.dq = dq; W.cov = bits; W.ovl = bits + MZ_CHOOSE_LDS_MAX / 8;
+    choose_read<ChooseLds>(P, P.ids[blockIdx.x], W, threadIdx.x);
+}
+__global__ void __launch_bounds__(64) minimizer_choose_slab_kernel(const MzChooseParams P) {
+    char* s = P.slab + (uint64_t)blockIdx.x * P.slab_stride; const uint64_t np = P.slab_np, words = P.slab_words;
+    ChooseWork<ChooseSlab> W;
+    W.key = (uint64_t*)s; s += 8 * np; W.ord = (uint64_t*)s; s += 8 * np; W.tmp = (uint64_t*)s; s += 8 * np; W.cov = (uint64_t*)s; s += 8 * words; W.ovl = (uint64_t*)s; s += 8 * words;
+    W.hits = (uint32_t*)s; s += 4 * np; W.run_hits = (uint32_t*)s; s += 4 * np; W.start = (uint32_t*)s; s += 4 * np; W.perm = (uint32_t*)s; s += 4 * np; W.off = (uint32_t*)s; s += 4 * np; W.dq = (uint32_t*)s;
+    for (uint32_t i = blockIdx.x; i < P.n; i += gridDim.x) { choose_read<ChooseSlab>(P, P.ids[i], W, threadIdx.x); __syncthreads(); }
+}
 // ---- one Path per read (chain_device.hpp): a lane per read for the bounds and the composition, a wavefront per read for the dense copy
 __global__ void __launch_bounds__(64) chain_stitch_kernel(const CsParams P, const int what) {
     cs_one(P, what, blockIdx.x * 64 + threadIdx.x);
@@ -1644,6 +1845,13 @@ public:
     int run_minimizer_seeds_of(const MzSeedsOfParams& p) override {
         hipSetDevice(dev);
         hipLaunchKernelGGL(minimizer_seeds_of_kernel, dim3((p.n + 256) / 256), dim3(256), 0, stream, p);
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_minimizer_choose(const MzChooseParams& p, uint32_t blocks) override {
+        hipSetDevice(dev);
+        if (!blocks) return VGK_OK;
+        if (p.slab) hipLaunchKernelGGL(minimizer_choose_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
+        else hipLaunchKernelGGL(minimizer_choose_kernel, dim3(blocks), dim3(64), 0, stream, p);
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
     int run_wfa_mask(const WProb* probs, const uint32_t* src_off, const char* raw, char* seqs, uint32_t n) override {

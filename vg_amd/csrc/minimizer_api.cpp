@@ -12,6 +12,7 @@
 #include "haplo.hpp"
 #include "host_parallel.hpp"
 #include "minimizer_device.hpp"
+#include "../../include/vgk_engine.h"
 
 using namespace vgk;
 
@@ -207,17 +208,14 @@ int vgk_minimizer_seeds(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vgk_h
 double vgk_minimizer_last_ms(vgk_ctx* ctx) { return ctx ? ctx->minimizer_ms : 0.0; }
 
 // ---- reads of any length: every minimizer listed; the seeds of those the caller takes (include/vgk.h) ----------------------------------------
-int vgk_minimizer_list(vgk_ctx* ctx, const vgk_minimizer_index* ix, const char* reads, const uint64_t* read_off, uint32_t n,
-                       uint64_t* minimizer_off, vgk_read_minimizer* minimizers, size_t cap, size_t* written) try {
-    if (!ctx || !ix || !vgk_tables_usable(ix->ctx, ctx) || !minimizer_off || (n && (!reads || !read_off)) || (!minimizers && cap)) return VGK_EINVAL;
-    if (written) *written = 0;
-    minimizer_off[0] = 0;
-    if (!n) return VGK_OK;
+// the list of n >= 1 reads made in HBM (callers hold ctx->mu): minimizer_off[n + 1] and *total on the host; the reads (behind 8 bytes of padding), their
+// offsets and the records stay in MZLIST_READS / MZLIST_READ_OFF / MZLIST_MINIMIZERS.  The records are written only when total <= cap
+static int list_on_device(vgk_ctx* ctx, const vgk_minimizer_index* ix, const char* reads, const uint64_t* read_off, uint32_t n, uint64_t* minimizer_off, size_t cap, size_t* total_out) {
+    *total_out = 0;
     for (uint32_t i = 0; i < n; ++i) if (read_off[i + 1] < read_off[i]) return VGK_EINVAL;
     const uint64_t bytes = read_off[n] - read_off[0];
     if (bytes > 0xfffffff0ull) return VGK_ETOOBIG;
     Backend* be = ctx->be.get();
-    std::lock_guard<std::mutex> lk(ctx->mu);
     // a read is cut into stretches of MZ_LIST_WINDOWS windows, a lane each (a 15 kbp read alone would keep one lane busy for 15 000 steps)
     std::vector<MzListItem> items; std::vector<uint64_t> item_first((size_t)n + 1, 0);
     const uint32_t k = ix->dev.k, w = ix->dev.w;
@@ -252,35 +250,38 @@ int vgk_minimizer_list(vgk_ctx* ctx, const vgk_minimizer_index* ix, const char* 
     if (rc) return rc;
     for (size_t i = 0; i < n1; ++i) minimizer_off[i] = first[item_first[i]];
     const size_t total = first[n_items];
-    if (written) *written = total;
+    *total_out = total;
     if (total > cap) return VGK_EOPS;
     if (!total) return VGK_OK;
     vgk_read_minimizer* d_out = (vgk_read_minimizer*)ctx->ensure_scratch(MZLIST_MINIMIZERS, sizeof(vgk_read_minimizer) * total);
     if (!d_out) return VGK_ENOMEM;
     P.out = d_out; P.pass = 2;
-    if ((rc = be->run_minimizer_list(P))) return rc;
-    return be->download(minimizers, d_out, sizeof(vgk_read_minimizer) * total);
+    return be->run_minimizer_list(P);
+}
+int vgk_minimizer_list(vgk_ctx* ctx, const vgk_minimizer_index* ix, const char* reads, const uint64_t* read_off, uint32_t n,
+                       uint64_t* minimizer_off, vgk_read_minimizer* minimizers, size_t cap, size_t* written) try {
+    if (!ctx || !ix || !vgk_tables_usable(ix->ctx, ctx) || !minimizer_off || (n && (!reads || !read_off)) || (!minimizers && cap)) return VGK_EINVAL;
+    if (written) *written = 0;
+    minimizer_off[0] = 0;
+    if (!n) return VGK_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    size_t total = 0;
+    const int rc = list_on_device(ctx, ix, reads, read_off, n, minimizer_off, cap, &total);
+    if (written) *written = total;
+    if (rc || !total) return rc;
+    return ctx->be->download(minimizers, ctx->scratch[MZLIST_MINIMIZERS].p, sizeof(vgk_read_minimizer) * total);
 } catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }
 
-int vgk_minimizer_seeds_of(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vgk_read_minimizer* minimizers, const uint8_t* take, size_t n_minimizers,
-                           uint64_t* seed_off, vgk_seed* seeds, size_t cap, size_t* written) try {
-    if (!ctx || !ix || !vgk_tables_usable(ix->ctx, ctx) || !seed_off || (n_minimizers && (!minimizers || !take)) || (!seeds && cap)) return VGK_EINVAL;
-    if (written) *written = 0;
-    seed_off[0] = 0;
-    if (!n_minimizers) return VGK_OK;
-    if (n_minimizers > 0xfffffff0ull) return VGK_ETOOBIG;
+// the seeds of the taken minimizers, list and choice in MZLIST_MINIMIZERS / MZLIST_TAKE already (callers hold ctx->mu; minimizers / take: the host's copies)
+static int seeds_of_on_device(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vgk_read_minimizer* minimizers, const uint8_t* take, size_t n_minimizers,
+                              uint64_t* seed_off, vgk_seed* seeds, size_t cap, size_t* written) {
     Backend* be = ctx->be.get();
-    std::lock_guard<std::mutex> lk(ctx->mu);
     const uint32_t n = (uint32_t)n_minimizers; const size_t n1 = (size_t)n + 1;
-    vgk_read_minimizer* d_min = (vgk_read_minimizer*)ctx->ensure_scratch(MZLIST_MINIMIZERS, sizeof(vgk_read_minimizer) * n_minimizers);
-    uint8_t* d_take = (uint8_t*)ctx->ensure_scratch(MZLIST_TAKE, n_minimizers + 16);
     uint32_t* d_tab = (uint32_t*)ctx->ensure_scratch(MZLIST_SEED_TAB, sizeof(uint32_t) * 2 * n1);
-    if (!d_min || !d_take || !d_tab) return VGK_ENOMEM;
+    if (!d_tab) return VGK_ENOMEM;
     MzSeedsOfParams P{};
-    P.index = ix->dev; P.mins = d_min; P.take = d_take; P.n = n; P.counts = d_tab; P.first = d_tab + n1; P.pass = 1;
-    int rc = be->upload(d_min, minimizers, sizeof(vgk_read_minimizer) * n_minimizers);
-    if (!rc) rc = be->upload(d_take, take, n_minimizers);
-    if (!rc) rc = be->run_minimizer_seeds_of(P);
+    P.index = ix->dev; P.mins = (const vgk_read_minimizer*)ctx->scratch[MZLIST_MINIMIZERS].p; P.take = (const uint8_t*)ctx->scratch[MZLIST_TAKE].p; P.n = n; P.counts = d_tab; P.first = d_tab + n1; P.pass = 1;
+    int rc = be->run_minimizer_seeds_of(P);
     // (a 32-bit prefix sum: the hits of the taken minimizers of one call stay below 2^32 — checked against the index's own size below)
     if (!rc) rc = be->scan_u32(d_tab, d_tab + n1, (uint32_t)n1);
     std::vector<uint32_t> first(n1);
@@ -299,6 +300,161 @@ int vgk_minimizer_seeds_of(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vg
     P.out = d_out; P.pass = 2;
     if ((rc = be->run_minimizer_seeds_of(P))) return rc;
     return be->download(seeds, d_out, sizeof(vgk_seed) * total);
+}
+int vgk_minimizer_seeds_of(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vgk_read_minimizer* minimizers, const uint8_t* take, size_t n_minimizers,
+                           uint64_t* seed_off, vgk_seed* seeds, size_t cap, size_t* written) try {
+    if (!ctx || !ix || !vgk_tables_usable(ix->ctx, ctx) || !seed_off || (n_minimizers && (!minimizers || !take)) || (!seeds && cap)) return VGK_EINVAL;
+    if (written) *written = 0;
+    seed_off[0] = 0;
+    if (!n_minimizers) return VGK_OK;
+    if (n_minimizers > 0xfffffff0ull) return VGK_ETOOBIG;
+    Backend* be = ctx->be.get();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    vgk_read_minimizer* d_min = (vgk_read_minimizer*)ctx->ensure_scratch(MZLIST_MINIMIZERS, sizeof(vgk_read_minimizer) * n_minimizers);
+    uint8_t* d_take = (uint8_t*)ctx->ensure_scratch(MZLIST_TAKE, n_minimizers + 16);
+    if (!d_min || !d_take) return VGK_ENOMEM;
+    int rc = be->upload(d_min, minimizers, sizeof(vgk_read_minimizer) * n_minimizers);
+    if (!rc) rc = be->upload(d_take, take, n_minimizers);
+    if (rc) return rc;
+    return seeds_of_on_device(ctx, ix, minimizers, take, n_minimizers, seed_off, seeds, cap, written);
 } catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }
+
+// ---- find_seeds' choice on the device (include/vgk_engine.h; minimizer_device.hpp: mz_choose_one is the rule) --------------------------------------
+namespace {
+// the policy as the kernels read it; its score table (the host's logarithm, as vgk_minimizer_set_policy makes it) goes to MZCHOOSE_TAB
+int choose_policy(vgk_ctx* ctx, const vgk_find_seeds_policy* p, MzChoosePolicy* Q) {
+    if (!p->hard_hit_cap || p->hard_hit_cap > 65535u || !(p->minimizer_score_fraction >= 0.0 && p->minimizer_score_fraction <= 1.0)) return VGK_EINVAL;
+    std::vector<double> tab((size_t)p->hard_hit_cap + 1, 0.0);
+    const double base = 1.0 + std::log((double)p->hard_hit_cap);
+    for (uint32_t h = 1; h <= p->hard_hit_cap; ++h) tab[h] = base - std::log((double)h);
+    for (uint32_t h = 2; h <= p->hard_hit_cap; ++h) if (!(tab[h] < tab[h - 1])) return VGK_EINVAL;      // (mz_choose_rank stands on it; consecutive logarithms are far more than an ulp apart)
+    if (!(tab[p->hard_hit_cap] > 0.0)) return VGK_EINVAL;
+    const double* d = ctx->scratch_dev<double>(MZCHOOSE_TAB, tab.data(), sizeof(double) * tab.size());
+    if (!d) return VGK_ENOMEM;
+    const int rc = ctx->be->sync();                                        // (tab may go)
+    if (rc) return rc;
+    Q->hit_cap = p->hit_cap; Q->hard_hit_cap = p->hard_hit_cap; Q->fraction = p->minimizer_score_fraction; Q->tab = d;
+    Q->max_unique_min = p->max_unique_min; Q->num_bp_per_min = p->num_bp_per_min; Q->flank = p->minimizer_coverage_flank; Q->exclude_overlapping = p->exclude_overlapping_min;
+    Q->window_count = p->minimizer_downsampling_window_count; Q->max_window = p->minimizer_downsampling_max_window_length;
+    Q->over_rank = mz_over_rank(tab.data(), p->hard_hit_cap);
+    return VGK_OK;
+}
+// the choice kernels over a list in HBM (P: everything but ids and the slab): the reads that fit LDS a workgroup each, the others over slabs
+int choose_on_device(vgk_ctx* ctx, MzChooseParams P, const uint64_t* read_off, const uint64_t* minimizer_off, uint32_t n) {
+    Backend* be = ctx->be.get();
+    std::vector<uint32_t> ids; std::vector<uint32_t> large;
+    uint64_t max_n = 0, max_L = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+        const uint64_t m = minimizer_off[r + 1] - minimizer_off[r], L = read_off[r + 1] - read_off[r];
+        if (!m) continue;
+        if (m > 0x80000000ull || L > 0xfffffff0ull) return VGK_ETOOBIG;
+        const uint64_t window = mz_choose_window(P.policy, L, P.k);
+        if (window && P.k > window) return VGK_EINVAL;                     // (find_seeds' crash_unless(length <= window))
+        if (m <= MZ_CHOOSE_LDS_MAX && L <= MZ_CHOOSE_LDS_BASES) ids.push_back(r);
+        else { large.push_back(r); max_n = std::max(max_n, m); max_L = std::max(max_L, L); }
+    }
+    const size_t n_lds = ids.size();
+    ids.insert(ids.end(), large.begin(), large.end());
+    if (ids.empty()) { ctx->minimizer_choose_ms = 0.0; return VGK_OK; }
+    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(MZCHOOSE_IDS, ids.data(), sizeof(uint32_t) * ids.size());
+    if (!d_ids) return VGK_ENOMEM;
+    uint32_t blocks = 0;
+    if (!large.empty()) {
+        uint64_t np = 1; while (np < max_n) np <<= 1;
+        P.slab_np = (uint32_t)np; P.slab_words = (uint32_t)((max_L + 64) / 64);
+        P.slab_stride = 48 * np + 16 * (uint64_t)P.slab_words;             // (minimizer_choose_slab_kernel's layout)
+        blocks = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(large.size(), 512), std::max<uint64_t>(1, (1ull << 30) / P.slab_stride));
+        P.slab = (char*)ctx->ensure_scratch(MZCHOOSE_SLAB, P.slab_stride * blocks);
+        if (!P.slab) return VGK_ENOMEM;
+    }
+    char* slab = P.slab;
+    be->watch(0);
+    P.ids = d_ids; P.n = (uint32_t)n_lds; P.slab = nullptr;
+    int rc = be->run_minimizer_choose(P, (uint32_t)n_lds);
+    if (!rc && !large.empty()) { P.ids = d_ids + n_lds; P.n = (uint32_t)large.size(); P.slab = slab; rc = be->run_minimizer_choose(P, blocks); }
+    be->watch(1);
+    if (!rc) rc = be->sync();                                              // (ids may go)
+    if (!rc) ctx->minimizer_choose_ms = be->watch_ms();
+    return rc;
+}
+}  // namespace
+
+int vgk_minimizer_choose(vgk_ctx* ctx, const vgk_find_seeds_policy* policy, uint32_t k, const char* reads, const uint64_t* read_off, uint32_t n,
+                         const uint64_t* minimizer_off, const vgk_read_minimizer* minimizers, uint8_t* verdict) try {
+    if (!ctx || !policy || !k || k > MZ_MAX_K || (n && (!read_off || !minimizer_off))) return VGK_EINVAL;
+    if (!n) return VGK_OK;
+    if (minimizer_off[0] != 0) return VGK_EINVAL;
+    for (uint32_t r = 0; r < n; ++r) {
+        if (read_off[r + 1] < read_off[r] || minimizer_off[r + 1] < minimizer_off[r]) return VGK_EINVAL;
+        if (minimizer_off[r + 1] > minimizer_off[r] && !minimizers) return VGK_EINVAL;
+        const uint64_t L = read_off[r + 1] - read_off[r];
+        for (uint64_t j = minimizer_off[r]; j < minimizer_off[r + 1]; ++j) {
+            if ((uint64_t)minimizers[j].offset + k > L) return VGK_EINVAL;
+            if (j > minimizer_off[r] && minimizers[j].offset < minimizers[j - 1].offset) return VGK_EINVAL;
+        }
+    }
+    const uint64_t total = minimizer_off[n], bytes = read_off[n] - read_off[0];
+    if (!total) return VGK_OK;
+    if (!verdict || (bytes && !reads)) return VGK_EINVAL;
+    if (total > 0xfffffff0ull || bytes > 0xfffffff0ull) return VGK_ETOOBIG;
+    Backend* be = ctx->be.get();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    MzChooseParams P{};
+    int rc = choose_policy(ctx, policy, &P.policy);
+    if (rc) return rc;
+    const size_t n1 = (size_t)n + 1;
+    std::vector<uint64_t> rel(n1);
+    for (size_t i = 0; i < n1; ++i) rel[i] = read_off[i] - read_off[0];
+    char* d_reads = ctx->scratch_dev<char>(MZLIST_READS, bytes ? reads + read_off[0] : nullptr, bytes);
+    const uint64_t* d_off = ctx->scratch_dev<uint64_t>(MZLIST_READ_OFF, rel.data(), sizeof(uint64_t) * n1);
+    const uint64_t* d_moff = ctx->scratch_dev<uint64_t>(MZCHOOSE_MIN_OFF, minimizer_off, sizeof(uint64_t) * n1);
+    const vgk_read_minimizer* d_min = ctx->scratch_dev<vgk_read_minimizer>(MZLIST_MINIMIZERS, minimizers, sizeof(vgk_read_minimizer) * total);
+    uint8_t* d_verdict = (uint8_t*)ctx->ensure_scratch(MZLIST_TAKE, total + 16);
+    if (!d_reads || !d_off || !d_moff || !d_min || !d_verdict) return VGK_ENOMEM;
+    P.k = k; P.reads = d_reads; P.read_off = d_off; P.min_off = d_moff; P.mins = d_min; P.verdict = d_verdict; P.as_take = 0;
+    if ((rc = choose_on_device(ctx, P, rel.data(), minimizer_off, n))) return rc;
+    return be->download(verdict, d_verdict, total);
+} catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }
+
+int vgk_minimizer_find_seeds(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vgk_find_seeds_policy* policy, const char* reads, const uint64_t* read_off, uint32_t n,
+                             uint64_t* minimizer_off, vgk_read_minimizer* minimizers, uint8_t* take, size_t cap_m,
+                             uint64_t* seed_off, vgk_seed* seeds, size_t cap_s, size_t written[2]) try {
+    if (!ctx || !ix || !policy || !vgk_tables_usable(ix->ctx, ctx) || !minimizer_off || !written || (n && (!reads || !read_off)) || (cap_m && (!minimizers || !take || !seed_off)) || (!seeds && cap_s)) return VGK_EINVAL;
+    written[0] = written[1] = 0;
+    minimizer_off[0] = 0;
+    if (seed_off) seed_off[0] = 0;
+    if (!n) return VGK_OK;
+    Backend* be = ctx->be.get();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    MzChooseParams P{};
+    int rc = choose_policy(ctx, policy, &P.policy);
+    if (rc) return rc;
+    // the list is made in HBM whatever room the caller has: the needed sizes of BOTH outputs are then known from one call
+    size_t total = 0;
+    if ((rc = list_on_device(ctx, ix, reads, read_off, n, minimizer_off, (size_t)-1, &total))) return rc;
+    written[0] = total;
+    if (!total) return VGK_OK;
+    const size_t n1 = (size_t)n + 1;
+    std::vector<uint64_t> rel(n1);
+    for (size_t i = 0; i < n1; ++i) rel[i] = read_off[i] - read_off[0];
+    const uint64_t* d_moff = ctx->scratch_dev<uint64_t>(MZCHOOSE_MIN_OFF, minimizer_off, sizeof(uint64_t) * n1);
+    uint8_t* d_take = (uint8_t*)ctx->ensure_scratch(MZLIST_TAKE, total + 16);
+    if (!d_moff || !d_take) return VGK_ENOMEM;
+    P.k = ix->dev.k; P.reads = (const char*)ctx->scratch[MZLIST_READS].p + 8; P.read_off = (const uint64_t*)ctx->scratch[MZLIST_READ_OFF].p; P.min_off = d_moff;
+    P.mins = (const vgk_read_minimizer*)ctx->scratch[MZLIST_MINIMIZERS].p; P.verdict = d_take; P.as_take = 1;
+    if ((rc = choose_on_device(ctx, P, rel.data(), minimizer_off, n))) return rc;
+    // list and choice come down (into the caller's arrays when they are large enough), the seeds of the taken are counted and written
+    std::vector<vgk_read_minimizer> own_m; std::vector<uint8_t> own_t; std::vector<uint64_t> own_s;
+    const bool fits = total <= cap_m;
+    if (!fits) { own_m.resize(total); own_t.resize(total); own_s.resize(total + 1); }
+    vgk_read_minimizer* hm = fits ? minimizers : own_m.data(); uint8_t* ht = fits ? take : own_t.data();
+    if ((rc = be->download(hm, P.mins, sizeof(vgk_read_minimizer) * total))) return rc;
+    if ((rc = be->download(ht, d_take, total))) return rc;
+    rc = seeds_of_on_device(ctx, ix, hm, ht, total, fits ? seed_off : own_s.data(), fits ? seeds : nullptr, fits ? cap_s : 0, &written[1]);
+    if (rc) return rc;
+    return fits ? VGK_OK : VGK_EOPS;
+} catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }
+
+double vgk_minimizer_choose_last_ms(vgk_ctx* ctx) { return ctx ? ctx->minimizer_choose_ms : 0.0; }
 
 }  // extern "C"

@@ -344,4 +344,158 @@ VGK_HD void mz_seeds_of_one(const MzSeedsOfParams& P, uint32_t j) {
     for (uint32_t h = 0; h < count; ++h) dst[h] = mz_seed(first == MZ_ONE ? one : P.index.pos[first + h], r.offset, m.reverse, P.index.k);
 }
 
+// ---- find_seeds' WHOLE choice for reads of any length (include/vgk_engine.h: vgk_minimizer_choose / vgk_minimizer_find_seeds) -----------------
+// select_minimizers of vg_amd/host/seed_policy.cpp:55-193 (reference src/minimizer_mapper.cpp:4109-4440) over a list as vgk_minimizer_list answers
+// it, every minimizer k bases long: the scores from the host-made table, the order (score descending, key, read position), the runs tied at the top
+// shuffled whenever there are two or more of them (with a unique-minimizer budget the order inside the tie decides who is taken: mz_tie_matters'
+// shortcut does not hold here) by the generator of mz_shuffle_top_ties seeded from the read's bytes as the caller gave them, window downsampling
+// (sample_minimal, seed_policy.cpp:17-53), and the filters in score order, run by run.  Two forms, as for mz_policy_select: mz_choose_one below is
+// the serial statement and the checker (one lane, scratch from the caller); backend_hip.hip's minimizer_choose_kernel is one wavefront per read.
+struct MzChoosePolicy {
+    uint32_t hit_cap, hard_hit_cap; double fraction; const double* tab;      // tab[h], h = 0 .. hard_hit_cap, as MzPolicy::tab
+    uint32_t max_unique_min, num_bp_per_min, flank, exclude_overlapping, window_count; uint64_t max_window;
+    uint32_t over_rank;                                                       // mz_over_rank(tab, hard_hit_cap): where 1.0 stands among the table's scores
+};
+// what the kernel keeps in LDS: a read of at most MZ_CHOOSE_LDS_MAX minimizers and MZ_CHOOSE_LDS_BASES bases is sorted and filtered there — keys 32 KiB,
+// (rank, position) words 16 KiB, the line of the downsampling sweep 8 KiB, two coverage bitmaps of 4 KiB: the 64 KiB a workgroup may declare, two
+// workgroups to a CU's 160 KiB; a 15 kbp read has about 2 500 minimizers.  Anything larger takes the same steps over a slab in HBM.
+constexpr uint32_t MZ_CHOOSE_LDS_MAX = 4096, MZ_CHOOSE_LDS_BASES = 32767;
+constexpr uint8_t MZ_TAKEN = 0, MZ_DOWNSAMPLED = 1, MZ_NO_HITS = 2, MZ_HARD_HIT_CAP = 3, MZ_OVERLAPPING = 4, MZ_MAX_MIN = 5, MZ_HIT_CAP = 6;      // SeedFilter of vg_amd/host/seed_policy.hpp
+struct MzChooseParams {
+    MzChoosePolicy policy; uint32_t k;
+    const char* reads; const uint64_t* read_off;                              // the reads' bytes as the caller gave them (they seed the shuffle)
+    const uint64_t* min_off; const vgk_read_minimizer* mins;                  // read r's minimizers: mins[min_off[r] .. min_off[r + 1]), by read offset
+    uint8_t* verdict; uint32_t as_take;                                       // per minimizer: the filter that dropped it (0 = taken), or (as_take) 1 = taken, 0 = dropped
+    const uint32_t* ids; uint32_t n;                                          // the reads of this launch
+    char* slab; uint64_t slab_stride; uint32_t slab_np, slab_words;           // the slab route: room per block for slab_np minimizers and bitmaps of slab_words words
+};
+VGK_HD double mz_choose_score(const MzChoosePolicy& Q, uint32_t hits) { return !hits ? 0.0 : (hits <= Q.hard_hit_cap ? Q.tab[hits] : 1.0); }
+// The scores as ranks, for the kernel's sort: the table falls strictly from tab[1] to tab[hard] (the host checks that when it makes it), so a minimizer
+// with 1 <= h <= hard hits has rank 2h, one without hits the last rank 2 hard + 2, and one beyond the hard cap (score 1.0) the rank this finds BY
+// COMPARING THE TABLE'S DOUBLES with 1.0: 2h where tab[h] == 1.0 bit for bit, otherwise the odd rank between its neighbours.  A smaller rank is a
+// higher score and equal ranks are equal doubles, so (rank, key, position) orders exactly as mz_better does.
+VGK_HD uint32_t mz_over_rank(const double* tab, uint32_t hard) {
+    if (tab[hard] > 1.0) return 2u * hard + 1u;
+    uint32_t h = hard; while (h > 1u && tab[h - 1u] <= 1.0) --h;              // the first h with tab[h] <= 1.0
+    return tab[h] == 1.0 ? 2u * h : 2u * h - 1u;
+}
+VGK_HD uint32_t mz_choose_rank(const MzChoosePolicy& Q, uint32_t hits) { return !hits ? 2u * Q.hard_hit_cap + 2u : (hits <= Q.hard_hit_cap ? 2u * hits : Q.over_rank); }
+VGK_HD uint32_t mz_minstd_first(uint32_t seed) { const uint32_t x = seed % 2147483647u; return x ? x : 1u; }
+VGK_HD uint32_t mz_minstd_next(uint32_t x) { return (uint32_t)(((uint64_t)x * 48271ull) % 2147483647ull); }
+// the downsampling window of a read of L bases (0: none), seed_policy.cpp:131-132
+VGK_HD uint64_t mz_choose_window(const MzChoosePolicy& Q, uint64_t L, uint32_t k) {
+    if (!Q.window_count) return 0;
+    const uint64_t w = L < (uint64_t)Q.window_count * k ? 0 : L / Q.window_count;
+    return w < Q.max_window ? w : Q.max_window;
+}
+// sample_minimal (seed_policy.cpp:17-53) as one sweep over a line kept in `dq` (room for n entries: every element enters once):
+// start(i), beats(a, b) — a displaces b —, sample(i).  Elements by start, all k long, k <= window.
+template <class DQ, class START, class BEATS, class SAMPLE>
+VGK_HD void mz_sample_minimal(uint32_t n, uint32_t k, uint64_t window, uint64_t L, DQ* dq, START start, BEATS beats, SAMPLE sample) {
+    uint32_t head = 0, tail = 0, next = 0;
+    auto admit = [&]() { while (tail > head && beats(next, (uint32_t)dq[tail - 1u])) --tail; dq[tail++] = (DQ)next; ++next; };
+    while (next < n && start(next) + k <= window) admit();
+    if (tail > head) sample((uint32_t)dq[head]);
+    uint64_t at = 0;
+    while (at + window < L) {
+        uint64_t to = L - window;
+        if (next < n) { uint64_t end = start(next) + k; if (end < window) end = window; if (end - window < to) to = end - window; }
+        if (tail > head && start((uint32_t)dq[head]) + 1u < to) to = start((uint32_t)dq[head]) + 1u;
+        while (tail > head && to > start((uint32_t)dq[head])) { ++head; if (tail > head && to > start((uint32_t)dq[head])) sample((uint32_t)dq[head]); }
+        while (next < n && to + window >= start(next) + k) admit();
+        if (tail > head) sample((uint32_t)dq[head]);
+        at = to;
+    }
+    if (tail > head) { const uint64_t tie = start((uint32_t)dq[head]); ++head; while (tail > head && start((uint32_t)dq[head]) == tie) { sample((uint32_t)dq[head]); ++head; } }
+}
+// scratch of the serial form: order, tmp, perm, dq: n entries each; start: n + 1; kept: n bytes; covered, covered_by_minimizer: L + 1 bytes each
+struct MzChooseScratch { uint32_t* order; uint32_t* tmp; uint32_t* start; uint32_t* perm; uint32_t* dq; uint8_t* kept; uint8_t* covered; uint8_t* covered_by_minimizer; };
+VGK_HD void mz_choose_one(const MzChooseParams& P, uint32_t r, const MzChooseScratch& S) {
+    const MzChoosePolicy& Q = P.policy;
+    const uint64_t a = P.min_off[r]; const uint32_t n = (uint32_t)(P.min_off[r + 1] - a);
+    if (!n) return;
+    const vgk_read_minimizer* m = P.mins + a; uint8_t* out = P.verdict + a;
+    const char* seq = P.reads + P.read_off[r]; const uint64_t L = P.read_off[r + 1] - P.read_off[r]; const uint32_t k = P.k;
+    auto score = [&](uint32_t i) { return mz_choose_score(Q, m[i].hits); };
+    auto before = [&](uint32_t x, uint32_t y) { return mz_better(score(x), m[x].key, x, score(y), m[y].key, y); };
+    // ---- the order: a merge sort between `order` and `tmp`
+    uint32_t* src = S.order; uint32_t* dst = S.tmp;
+    for (uint32_t i = 0; i < n; ++i) src[i] = i;
+    for (uint64_t width = 1; width < n; width *= 2) {
+        for (uint64_t lo = 0; lo < n; lo += 2 * width) {
+            const uint64_t mid = lo + width < n ? lo + width : n, hi = lo + 2 * width < n ? lo + 2 * width : n;
+            uint64_t x = lo, y = mid, o = lo;
+            while (x < mid && y < hi) dst[o++] = before(src[y], src[x]) ? src[y++] : src[x++];
+            while (x < mid) dst[o++] = src[x++];
+            while (y < hi) dst[o++] = src[y++];
+        }
+        uint32_t* t = src; src = dst; dst = t;
+    }
+    if (src != S.order) for (uint32_t i = 0; i < n; ++i) S.order[i] = src[i];
+    uint32_t* order = S.order;
+    // ---- the runs tied at the top, shuffled when there are two or more
+    { uint32_t runs = 0, e = 0; const double s0 = score(order[0]);
+      while (e < n && score(order[e]) == s0) { S.start[runs] = e; S.perm[runs] = runs; ++runs; const uint64_t key = m[order[e]].key; while (e < n && m[order[e]].key == key) ++e; }
+      S.start[runs] = e;
+      if (runs >= 2u) {
+          uint32_t seed = 0; for (uint64_t i = 0; i < L; ++i) seed = seed * 13u + (uint32_t)(uint8_t)seq[i];
+          uint32_t x = mz_minstd_first(seed);
+          for (uint32_t i = 1; i < runs; ++i) { x = mz_minstd_next(x); const uint32_t j = x % (i + 1u); const uint32_t t = S.perm[j]; S.perm[j] = S.perm[i]; S.perm[i] = t; }
+          uint32_t at = 0;
+          for (uint32_t i = 0; i < runs; ++i) for (uint32_t q = S.start[S.perm[i]]; q < S.start[S.perm[i] + 1u]; ++q) S.tmp[at++] = order[q];
+          for (uint32_t q = 0; q < e; ++q) order[q] = S.tmp[q];
+      } }
+    const bool score_filter = Q.hit_cap != 0 || Q.fraction != 1.0;
+    double target = 0.0, selected = 0.0;
+    if (score_filter) { double base = 0.0; for (uint32_t q = 0; q < n; ++q) base = mz_add(base, score(order[q])); target = mz_add(mz_mul(base, Q.fraction), 0.000001); }
+    // ---- window downsampling, in read order
+    bool downsampling = false;
+    const uint64_t window = mz_choose_window(Q, L, k);
+    if (window) {
+        for (uint32_t i = 0; i < n; ++i) S.kept[i] = 0;
+        mz_sample_minimal(n, k, window, L, S.dq, [&](uint32_t i) { return (uint64_t)m[i].offset; },
+            [&](uint32_t x, uint32_t y) { if (!m[x].hits) return false; if (!m[y].hits) return true; return score(x) > score(y) || (score(x) == score(y) && m[x].key < m[y].key); },
+            [&](uint32_t i) { S.kept[i] = 1; downsampling = true; });
+    }
+    // ---- the filters, in score order, run by run
+    for (uint64_t p = 0; p <= L; ++p) { S.covered[p] = 0; S.covered_by_minimizer[p] = 0; }
+    uint64_t taken = 0, worst_kept_hits = 0, run_hits = 0;
+    const uint64_t by_read_length = Q.num_bp_per_min ? L / Q.num_bp_per_min : 0, budget = Q.max_unique_min > by_read_length ? Q.max_unique_min : by_read_length;
+    uint32_t run_end = 0; bool taking_run = false;
+    for (uint32_t at = 0; at < n; ++at) {
+        if (at >= run_end) {
+            run_end = at + 1; run_hits = m[order[at]].hits;
+            while (run_end < n && m[order[run_end]].key == m[order[at]].key) { run_hits += m[order[run_end]].hits; ++run_end; }
+            taking_run = false;
+        }
+        const uint32_t i = order[at]; const uint64_t off = m[i].offset, hits = m[i].hits;
+        uint8_t failed = MZ_TAKEN;
+        if (downsampling && !S.kept[i]) failed = MZ_DOWNSAMPLED;
+        else if (!hits) failed = MZ_NO_HITS;
+        else if (run_hits > Q.hard_hit_cap) failed = MZ_HARD_HIT_CAP;
+        if (!failed && Q.exclude_overlapping) {
+            const uint64_t e = off + k < L ? off + k : L, stop = off + k < L + 1 ? off + k : L + 1;
+            if (S.covered_by_minimizer[off] || S.covered_by_minimizer[e]) failed = MZ_OVERLAPPING;
+            else for (uint64_t p = off; p < stop; ++p) S.covered_by_minimizer[p] = 1;
+        }
+        if (!failed && Q.max_unique_min != 0) {
+            const uint64_t lo = off < Q.flank ? 0 : off - Q.flank, hi = off + k + Q.flank < L ? off + k + Q.flank : L;
+            if (taken < budget) { for (uint64_t p = lo; p < hi; ++p) S.covered[p] = 1; if (hits > worst_kept_hits) worst_kept_hits = hits; }
+            else if (hits > worst_kept_hits) failed = MZ_MAX_MIN;
+            else {
+                bool fresh = true;
+                for (uint64_t p = lo; p < hi && fresh; ++p) fresh = !S.covered[p];
+                if (!fresh) failed = MZ_MAX_MIN; else for (uint64_t p = lo; p < hi; ++p) S.covered[p] = 1;
+            }
+        }
+        if (!failed && score_filter) {
+            const double sc = score(i);
+            if (hits <= Q.hit_cap || (run_hits <= Q.hard_hit_cap && mz_add(selected, sc) <= target) || taking_run) selected = mz_add(selected, sc);
+            else { failed = MZ_HIT_CAP; target = selected; }
+        }
+        out[i] = P.as_take ? (failed ? 0 : 1) : failed;
+        if (!failed) { taking_run = true; ++taken; }
+    }
+}
+
 }  // namespace vgk

@@ -37,6 +37,9 @@ enum Slot : int {
     // ctx->sets.reads then points there too).  MZLIST_*: vgk_minimizer_list and vgk_minimizer_seeds_of (nothing stays)
     SEEDED_READS, SEEDED_READ_OFF, SEEDED_TAB, SEEDED_SEEDS,
     MZLIST_READS, MZLIST_READ_OFF, MZLIST_TAB, MZLIST_ITEMS, MZLIST_MINIMIZERS, MZLIST_TAKE, MZLIST_SEED_TAB, MZLIST_SEEDS,
+    // vgk_minimizer_choose / vgk_minimizer_find_seeds (nothing stays): they work on the MZLIST_* buffers — the reads, the list, MZLIST_TAKE for the
+    // verdicts — plus the minimizers' offsets per read, the score table, the reads of a launch and the slab of the reads too large for LDS
+    MZCHOOSE_MIN_OFF, MZCHOOSE_TAB, MZCHOOSE_IDS, MZCHOOSE_SLAB,
     // ---- gssw_wide_api.cpp, chain_api.cpp (nothing stays)
     WIDE_PROBS, WIDE_ORDER, WIDE_COLINFO, WIDE_PROF, WIDE_NODES, WIDE_PREDS, WIDE_SCRATCH, WIDE_CARRY, WIDE_TB, WIDE_BEST, WIDE_RESULTS, WIDE_OPS,
     CHAIN_UP, CHAIN_TAB, CHAIN_RES, CHAIN_WORK_M, CHAIN_WORK_E, CHAIN_OUT_M, CHAIN_OUT_E,

@@ -417,12 +417,20 @@ GIRAFFE_LONG_READ_POLICY = dict(hit_cap=10, hard_hit_cap=500, max_unique_min=500
                                 max_window_length=(1 << 62), score_fraction=0.9)
 
 
-def seed_long_reads(eng, mindex, reads, read_off, k, policy=None, threads=0):
+def seed_long_reads(eng, mindex, reads, read_off, k, policy=None, threads=0, choice="host"):
     """MinimizerMapper::find_minimizers + find_seeds for reads of any length (src/minimizer_mapper.cpp:3918-4440): vgk_minimizer_list, the host shim's
     select_minimizers over every read's list (every filter, max_unique_min / num_bp_per_min included: :4162, :4312-4320), vgk_minimizer_seeds_of.
+    choice="device": the same three steps in one call with the choice made by the engine's kernels (vgk_minimizer_find_seeds, include/vgk_engine.h) —
+    no host library, no host threads, the list and the choice never leave HBM between the steps.
     -> dict(minimizer_off, minimizers, take, seed_off (per minimizer), seeds, seeds_per_read)"""
     P = dict(GIRAFFE_LONG_READ_POLICY, **(policy or {}))
     reads = np.ascontiguousarray(reads, dtype=np.uint8); read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    if choice == "device":
+        moff, recs, take, soff, seeds = eng.minimizer_find_seeds(mindex, P, reads, read_off)
+        per_read = soff[moff[1:].astype(np.int64)] - soff[moff[:-1].astype(np.int64)]
+        return dict(minimizer_off=moff, minimizers=recs, take=take, seed_off=soff, seeds=seeds, seeds_per_read=per_read)
+    if choice != "host":
+        raise ValueError("choice: 'host' or 'device'")
     moff, recs = eng.minimizer_list(mindex, reads, read_off)
     h = _host_lib()
     h.vgh_select_minimizers_of_reads.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]
