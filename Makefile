@@ -44,15 +44,16 @@ clean:
 
 .PHONY: all lib host oracle clean
 
-# test-only: CPU lock-step emulation of the HIP lane code behind the same C ABI
+# test-only: CPU lock-step emulation of the HIP lane code behind the same C ABI (VGK_PK_CHECK: pk16.hpp's full-width adds and subtracts count
+# every call that carries or borrows across the halves)
 emu: tests/emu/libvgamd_emu.so
 EMU_OBJS := $(patsubst vg_amd/csrc/%.cpp,tests/emu/obj/%.o,$(wildcard vg_amd/csrc/*.cpp)) tests/emu/obj/backend_emu.o
 tests/emu/obj/%.o: vg_amd/csrc/%.cpp $(LIB_HDRS)
 	@mkdir -p tests/emu/obj
-	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -c $< -o $@
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -DVGK_PK_CHECK -c $< -o $@
 tests/emu/obj/backend_emu.o: tests/emu/backend_emu.cpp $(LIB_HDRS)
 	@mkdir -p tests/emu/obj
-	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -c $< -o $@
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -DVGK_PK_CHECK -c $< -o $@
 tests/emu/libvgamd_emu.so: $(EMU_OBJS)
 	$(CXX) -shared -o $@ $(EMU_OBJS) -lpthread
 .PHONY: emu

@@ -72,6 +72,11 @@ double vgk_minimizer_choose_last_ms(vgk_ctx* ctx);
  * did not speculate ("speculation with feedback"). */
 int vgk_batch_refill_stats(vgk_batch* batch, uint64_t out[5]);
 
+/* The constant the rows of this batch's speculative first fill carry (the offset form of the rows), pre-multiplied by the score scale;
+ * 0 when the batch does not speculate or that fill runs the saturating rows (the scoring leaves no room for a constant, or VGAMD_NO_OFFSET_ROWS was set
+ * when the batch was packed). */
+uint32_t vgk_batch_row_offset(vgk_batch* batch);
+
 #ifdef __cplusplus
 }
 #endif

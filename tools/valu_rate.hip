@@ -37,6 +37,23 @@ __global__ void k_min16(uint32_t* p)   { BODY("v_min_u16 %0, %0, %1") }
 __global__ void k_sub16(uint32_t* p)   { BODY("v_sub_u16 %0, %0, %1") }
 __global__ void k_add16s(uint32_t* p)  { BODY("v_add_u16_sdwa %0, %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_1") }
 __global__ void k_pklshl(uint32_t* p)  { BODY("v_pk_lshlrev_b16 %0, 3, %0 op_sel_hi:[0,1]") }
+// the offset rows of the speculative first fill (gssw_device.hpp: gssw_row_offset): the third input / the addend from a scalar register, the three-input
+// add, and a stream shaped like one row — four full-rate adds / subtracts among three v_pk_maximum3_f16, a v_perm_b32 and a v_pk_mad_u16 (two chains)
+#define BODY_S(ASM) \
+    uint32_t a[8]; for (int i = 0; i < 8; ++i) a[i] = p[threadIdx.x + i * 64]; uint32_t b = p[1]; const uint32_t c = __builtin_amdgcn_readfirstlane(p[2]); \
+    for (int it = 0; it < N_ITER; ++it) { REP16( \
+        asm volatile(ASM : "+v"(a[0]) : "v"(b), "s"(c)); asm volatile(ASM : "+v"(a[1]) : "v"(b), "s"(c)); \
+        asm volatile(ASM : "+v"(a[2]) : "v"(b), "s"(c)); asm volatile(ASM : "+v"(a[3]) : "v"(b), "s"(c)); ) } \
+    uint32_t r = 0; for (int i = 0; i < 8; ++i) r += a[i]; p[threadIdx.x] = r;
+#define ROW_ASM "v_perm_b32 %0, %0, %1, %1\n v_add_u32 %0, %0, %1\n v_sub_u32 %0, %0, %1\n v_pk_maximum3_f16 %0, %0, %1, %1\n v_sub_u32 %0, %0, %1\n" \
+                "v_pk_maximum3_f16 %0, %0, %1, %2\n v_sub_u32 %0, %0, %1\n v_pk_maximum3_f16 %0, %0, %1, %2\n v_pk_mad_u16 %0, %0, 4, %2 op_sel_hi:[1,0,1]"
+__global__ void k_sub(uint32_t* p)      { BODY("v_sub_u32 %0, %0, %1") }
+__global__ void k_pkmax3(uint32_t* p)   { BODY("v_pk_maximum3_f16 %0, %0, %1, %2") }
+__global__ void k_pkmax3s(uint32_t* p)  { BODY_S("v_pk_maximum3_f16 %0, %0, %1, %2") }
+__global__ void k_pkmads(uint32_t* p)   { BODY_S("v_pk_mad_u16 %0, %0, 4, %2 op_sel_hi:[1,0,1]") }
+__global__ void k_add3(uint32_t* p)     { BODY("v_add3_u32 %0, %0, %1, %2") }
+__global__ void k_add3s(uint32_t* p)    { BODY_S("v_add3_u32 %0, %0, %1, %2") }
+__global__ void k_row(uint32_t* p)      { BODY_S(ROW_ASM) }
 template <class F> void run(const char* name, F f, uint32_t* d, int per_iter) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     const int blocks = 256 * 8;   // 8 blocks of 256 threads per CU = 8 waves per SIMD
@@ -56,5 +73,7 @@ int main() {
     run("and_b32", k_and, d, 1); run("or_b32", k_or, d, 1); run("bfi_b32", k_bfi, d, 1); run("mov_b32", k_mov, d, 1);
     run("lshlrev_b32", k_lshl, d, 1); run("and_or_b32", k_andor, d, 1); run("min_u16", k_min16, d, 1); run("sub_u16", k_sub16, d, 1);
     run("add_u16_sdwa", k_add16s, d, 1); run("pk_lshlrev", k_pklshl, d, 1);
+    run("sub_u32", k_sub, d, 1); run("pk_max3_f16", k_pkmax3, d, 1); run("pk_max3_f16_s", k_pkmax3s, d, 1); run("pk_mad_u16_s", k_pkmads, d, 1);
+    run("add3_u32", k_add3, d, 1); run("add3_u32_s", k_add3s, d, 1); run("offset_row/9", k_row, d, 9);
     return 0;
 }

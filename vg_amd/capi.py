@@ -1100,6 +1100,13 @@ class Batch:
         self.eng._check(f(self.h, out), "vgk_batch_refill_stats")
         return dict(zip(("waves", "steps", "missed", "bounded", "broken"), (int(v) for v in out)))
 
+    def row_offset(self):
+        """the constant (times the score scale) that the rows of this batch's speculative first fill carry in their offset form; 0 when the
+        batch does not speculate or that fill runs the saturating rows.  Engine library only."""
+        f = self.eng.lib.vgk_batch_row_offset
+        f.restype = ctypes.c_uint32; f.argtypes = [ctypes.c_void_p]
+        return int(f(self.h))
+
     def speculated(self):
         """did the last run fill without traceback codes first (the speculative fill; the context's feedback decides per run)"""
         self.eng.lib.vgk_batch_speculated.argtypes = [ctypes.c_void_p]

@@ -60,7 +60,8 @@ struct TbStage {
 
 // CODES = false: the recurrence alone and nothing of a traceback (GsswParams::spec_fill's first fill)
 // NOKEY: the second fill of a speculative batch (spec_fill == 2) — codes only; the end cells are the first fill's, nothing is tracked or published
-template <int K, bool S8, bool REWALK, bool CODES = true, bool KEY3 = false, bool NOKEY = false>
+// OFFS: a KEY3 first fill whose rows run in the offset form (gssw_device.hpp: gssw_row_offset; GsswParams::row_off != 0)
+template <int K, bool S8, bool REWALK, bool CODES = true, bool KEY3 = false, bool NOKEY = false, bool OFFS = false>
 __global__ __launch_bounds__(256, (K <= 16 ? 4 : 3)) void gssw_fill_kernel(const GsswParams P) {
     constexpr uint32_t REC = (K + 3) / 4;   // dwords per (step, lane) traceback record
     __shared__ __attribute__((aligned(16))) uint32_t stage_lds[4][REWALK ? 64u * TB_BND_CHUNK * 2u : (TB_TILE > 1 ? TbStage<K>::DWORDS : 256u)];      // (also the fused walk's best keys, below)
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(256, (K <= 16 ? 4 : 3)) void gssw_fill_kernel(const
     __shared__ uint32_t pb_lds[4][64 * K];      // read B's profile words, [row][lane] per wavefront (gssw_device.hpp: VGK_PB_LDS)
     s.PBL = (typename Lane<K>::lds_u32*)(pb_lds[threadIdx.x >> 6] + lane);
 #endif
-    lane_init<K, NOKEY ? 1 : 0>(s, P, wd, lane);
+    lane_init<K, NOKEY ? 1 : 0, OFFS ? 1 : 0>(s, P, wd, lane);
     asm volatile("" : "+v"(s.one));   // keep min(x,1) a packed min instead of cmp+cndmask
     uint32_t* tb = P.want_tb ? P.tb : nullptr;
     TbStage<K> stage{stage_lds[threadIdx.x >> 6]};
@@ -94,17 +95,17 @@ __global__ __launch_bounds__(256, (K <= 16 ? 4 : 3)) void gssw_fill_kernel(const
         for (; t < steady_from; ++t) {
             if ((t & 3u) == 0) lane_prefetch(s, P, t);
             const uint32_t rh = from_lane_above(s.out_h), rf = from_lane_above(s.out_f), ri = from_lane_above(s.info);
-            lane_step<K, S8, false, KEY3>(s, P, t, rh, rf, ri, nullptr, nullptr);
+            lane_step<K, S8, false, KEY3, false, false, OFFS ? 1 : 0>(s, P, t, rh, rf, ri, nullptr, nullptr);
         }
         for (; t < steady_to; ++t) {
             if ((t & 3u) == 0) lane_prefetch(s, P, t);
             const uint32_t rh = from_lane_above(s.out_h), rf = from_lane_above(s.out_f), ri = from_lane_above(s.info);
-            lane_step<K, S8, false, KEY3, false, true>(s, P, t, rh, rf, ri, nullptr, nullptr);
+            lane_step<K, S8, false, KEY3, false, true, OFFS ? 1 : 0>(s, P, t, rh, rf, ri, nullptr, nullptr);
         }
         for (; t < wd.n_steps; ++t) {
             if ((t & 3u) == 0) lane_prefetch(s, P, t);
             const uint32_t rh = from_lane_above(s.out_h), rf = from_lane_above(s.out_f), ri = from_lane_above(s.info);
-            lane_step<K, S8, false, KEY3>(s, P, t, rh, rf, ri, nullptr, nullptr);
+            lane_step<K, S8, false, KEY3, false, false, OFFS ? 1 : 0>(s, P, t, rh, rf, ri, nullptr, nullptr);
         }
     }
     for (uint32_t t = 0; CODES && t < wd.n_steps; ++t) {
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(256, (K <= 16 ? 4 : 3)) void gssw_fill_kernel(const
         if constexpr (!CODES) {
         } else if constexpr (REWALK) {
             // the recurrence alone; what the traceback needs to run a window of it again (gssw_device.hpp, TB_REWALK)
-            lane_step<K, S8, false>(s, P, t, rh, rf, ri, nullptr, nullptr);
+            lane_step<K, S8, false, false, false, false, 0>(s, P, t, rh, rf, ri, nullptr, nullptr);
             if (tb) {
                 // boundary rows: TB_BND_CHUNK steps gathered per lane in LDS (slot index XOR lane: the per-step writes and the flush's reads
                 // both spread over the banks), then each lane's chunk leaves as one 128-byte line of the lane-major layout
@@ -135,10 +136,10 @@ __global__ __launch_bounds__(256, (K <= 16 ? 4 : 3)) void gssw_fill_kernel(const
                 lane_store_checkpoint<K>(s, P, wd, t, lane);
             }
         } else if constexpr (TB_TILE > 1) {
-            lane_step<K, S8, true, false, NOKEY>(s, P, t, rh, rf, ri, tb ? stage.slot_a(t, lane) : nullptr, stage.slot_b(t, lane));
+            lane_step<K, S8, true, false, NOKEY, false, 0>(s, P, t, rh, rf, ri, tb ? stage.slot_a(t, lane) : nullptr, stage.slot_b(t, lane));
             if (tb && ((t % TB_TILE) == TB_TILE - 1u || t + 1u == wd.n_steps)) stage.flush(tb + tb_tile_base(wd.tb_off, t, REC), lane);
         } else
-            lane_step<K, S8, true, false, NOKEY>(s, P, t, rh, rf, ri, tb ? tb + tb_dword(wd.tb_off, t, lane, REC, 0) : nullptr, tb ? tb + tb_dword(wd.tb_off, t, lane, REC, 4) : nullptr);
+            lane_step<K, S8, true, false, NOKEY, false, 0>(s, P, t, rh, rf, ri, tb ? tb + tb_dword(wd.tb_off, t, lane, REC, 0) : nullptr, tb ? tb + tb_dword(wd.tb_off, t, lane, REC, 4) : nullptr);
     }
     if constexpr (NOKEY) return;
     if (REWALK || !CODES || !P.fused) {
@@ -1457,7 +1458,8 @@ public:
         const dim3 grid((p.wave_count + 3) / 4), block(256);
         const bool s8 = p.scale == 8, re = p.tb_mode == TB_REWALK;
         if (p.spec_fill == 1) {                                      // the first fill of a speculative batch: no codes
-            if (s8 && p.key3) hipLaunchKernelGGL((gssw_fill_kernel<K, true, false, false, true>), grid, block, 0, stream, p);
+            if (s8 && p.key3 && p.row_off) hipLaunchKernelGGL((gssw_fill_kernel<K, true, false, false, true, false, true>), grid, block, 0, stream, p);
+            else if (s8 && p.key3) hipLaunchKernelGGL((gssw_fill_kernel<K, true, false, false, true>), grid, block, 0, stream, p);
             else if (s8) hipLaunchKernelGGL((gssw_fill_kernel<K, true, false, false>), grid, block, 0, stream, p); else hipLaunchKernelGGL((gssw_fill_kernel<K, false, false, false>), grid, block, 0, stream, p);
             return VGK_OK;
         }

@@ -141,6 +141,8 @@ struct GsswParams {
                                 // bits already weighted and they merge with full-rate ORs instead of v_pk_mad.
     uint32_t xoff;              // XOFF * scale
     int8_t   matrix[25];
+    uint32_t row_off;           // a key3 batch's first fill runs its rows in the offset form (lane_row): every H / E / F of that fill carries this constant (scaled;
+                                // gssw_row_offset), 0 = the saturating rows.  (Last: no other field moves.)
 };
 
 VGK_HD uint32_t rep2(uint32_t x) { return (x & 0xffffu) * 0x00010001u; }
@@ -223,8 +225,11 @@ VGK_HD uint32_t ci_word(uint32_t w, uint32_t t, uint32_t R) {
 }
 // SECOND: whether the reads start at their ProbDesc::col0 — 1: yes (the kernel of a speculative batch's second fill), 0: no (every other kernel: nothing
 // of it is compiled into them, the first fill's registers are what they were), -1: where GsswParams::spec_fill says so (the emulator's one fill routine)
-template <int K, int SECOND = -1>
+// OFS: whether the lane state starts at the offset rows' floor (GsswParams::row_off; lane_row) — 1: yes (the kernel of a key3 batch's first fill in that form),
+// 0: no, -1: where GsswParams says so (the emulator)
+template <int K, int SECOND = -1, int OFS = -1>
 VGK_HD void lane_init(Lane<K>& s, const GsswParams& P, const WaveDesc& wd, uint32_t lane_id) {
+    const uint32_t floor2 = (OFS > 0 || (OFS < 0 && P.key3 && P.spec_fill == 1)) ? rep2(P.row_off) : 0u;
     const uint32_t q = lane_id / wd.G;
     s.g = lane_id - q * wd.G;
     s.Lpad = wd.G * K;
@@ -260,9 +265,9 @@ VGK_HD void lane_init(Lane<K>& s, const GsswParams& P, const WaveDesc& wd, uint3
         uint32_t pa = 0, pb = 0;
         if (row < s.LA) pa = poA != 0xffffffffu ? P.prof[poA + row] : pw.of_row(P.reads[roA + row]) + 0x01010101u * row_bonus(s.bsA, s.beA, row, s.LA);
         if (row < s.LB) pb = poB != 0xffffffffu ? P.prof[poB + row] : pw.of_row(P.reads[roB + row]) + 0x01010101u * row_bonus(s.bsB, s.beB, row, s.LB);
-        s.PA[m] = pa; s.set_pb(m, pb); s.H[m] = 0; s.E[m] = 0;
+        s.PA[m] = pa; s.set_pb(m, pb); s.H[m] = floor2; s.E[m] = floor2;
     }
-    s.out_h = 0; s.out_f = 0; s.info = CI_INVALID2; s.prev_rh = 0;
+    s.out_h = floor2; s.out_f = floor2; s.info = CI_INVALID2; s.prev_rh = floor2;
     s.best_lo = s.best_hi = 0; s.step_lo = s.step_hi = 0;
     s.nodeA = SECOND != 0 ? n0A - 1u : 0xffffffffu; s.nodeB = SECOND != 0 ? n0B - 1u : 0xffffffffu;
     s.one = 0x00010001u;
@@ -297,14 +302,16 @@ static inline uint32_t scratch_load(const uint32_t* p) { return *p; }
 
 // SEED_SLOW: seed column = element-wise max over the predecessors' saved last
 // columns (gssw_create_seed_*); HALF = 0 for read A (low halves), 1 for read B.
+// floor2 = the offset rows' constant in both halves (lane_row; 0 in every other fill): the lane state carries it, the scratch does not.
 template <int HALF, int K>
-VGK_HD void seed_from_scratch(Lane<K>& s, const GsswParams& P, uint32_t prob, uint32_t node, uint32_t& diag0) {
+VGK_HD void seed_from_scratch(Lane<K>& s, const GsswParams& P, uint32_t prob, uint32_t node, uint32_t& diag0, uint32_t floor2) {
     const ProbDesc& d = P.probs[prob];
     const NodeRec& nr = P.nodes[d.node_off + node];
     const uint32_t keep = HALF == 0 ? 0xffff0000u : 0x0000ffffu;     // the other read's half stays
+    const uint32_t fl = floor2 & ~keep;                              // (a batch in the offset form has no X-drop problem: the root column below sees fl = 0)
 #pragma unroll
-    for (int m = 0; m < K; ++m) { s.H[m] &= keep; s.E[m] &= keep; }
-    diag0 &= keep;
+    for (int m = 0; m < K; ++m) { s.H[m] = (s.H[m] & keep) | fl; s.E[m] = (s.E[m] & keep) | fl; }
+    diag0 = (diag0 & keep) | fl;
     if (nr.n_pred == 0 && (d.flags & 15u) == VGK_XDROP_PINNED) {
         // dozeu root column (dz_align_init): nothing consumed = 0, i leading inserted bases = -(go + (i-1) ge)
         // for i <= max_gap cells, unreachable beyond; E of the next column opens a deletion from it.
@@ -332,25 +339,25 @@ VGK_HD void seed_from_scratch(Lane<K>& s, const GsswParams& P, uint32_t prob, ui
         for (int m = 0; m < K; ++m) {
             const uint32_t v = scratch_load(base + m);     // lo16 = H, hi16 = E-next of the predecessor's last column
             // a packed max against a value whose other half is 0 leaves the other read untouched
-            s.H[m] = pk_max(s.H[m], HALF == 0 ? (v & 0xffffu) : (v << 16));
-            s.E[m] = pk_max(s.E[m], HALF == 0 ? (v >> 16) : (v & 0xffff0000u));
+            s.H[m] = pk_max(s.H[m], (HALF == 0 ? (v & 0xffffu) : (v << 16)) + fl);
+            s.E[m] = pk_max(s.E[m], (HALF == 0 ? (v >> 16) : (v & 0xffff0000u)) + fl);
         }
         if (s.g > 0) {
             const uint32_t v = scratch_load(base - 1);
-            diag0 = pk_max(diag0, HALF == 0 ? (v & 0xffffu) : (v << 16));
+            diag0 = pk_max(diag0, (HALF == 0 ? (v & 0xffffu) : (v << 16)) + fl);
         }
     }
 }
 
 template <int HALF, int K>
-VGK_HD void store_to_scratch(const Lane<K>& s, const GsswParams& P, uint32_t prob, uint32_t node) {
+VGK_HD void store_to_scratch(const Lane<K>& s, const GsswParams& P, uint32_t prob, uint32_t node, uint32_t floor2) {
     const ProbDesc& d = P.probs[prob];
     const NodeRec& nr = P.nodes[d.node_off + node];
     uint32_t* base = P.scratch + d.scratch_off + (uint32_t)nr.slot * s.Lpad + s.g * K;
 #pragma unroll
     for (int m = 0; m < K; ++m) {
-        uint32_t h = HALF == 0 ? (s.H[m] & 0xffffu) : (s.H[m] >> 16);
-        uint32_t e = HALF == 0 ? (s.E[m] & 0xffffu) : (s.E[m] >> 16);
+        uint32_t h = (HALF == 0 ? (s.H[m] & 0xffffu) : (s.H[m] >> 16)) - (floor2 & 0xffffu);
+        uint32_t e = (HALF == 0 ? (s.E[m] & 0xffffu) : (s.E[m] >> 16)) - (floor2 & 0xffffu);
         base[m] = h | (e << 16);
     }
 }
@@ -398,6 +405,30 @@ VGK_HD uint64_t tb_dword(uint64_t tb_off, uint32_t t, uint32_t lane, uint32_t re
 VGK_HD bool gssw_key3_ok(uint32_t scale, bool quality_adjusted, bool any_xdrop, uint32_t longest_read, uint32_t max_score, uint32_t max_bonus) {
     return scale == 8u && !quality_adjusted && !any_xdrop && (uint64_t)longest_read * max_score + 2ull * max_bonus <= 990ull;
 }
+// The offset form of the speculative first fill's rows (OFS below; GsswParams::row_off = A, scaled): every H / E / F of that fill is carried as value + A in both
+// halves.  With A at least every constant that is ever subtracted from a value at the floor — go, ge, the profile bias — no subtraction can borrow from the
+// other read's half, so the four saturating v_pk_sub_u16 of a row become full-rate v_sub_u32 (pk_sub_nb); the zero floor moves into the E and F maxima as the third
+// input of v_pk_maximum3_f16 (the constant A, from a scalar register, at the cost of the two-input maximum), and H = max3(d, E, F) >= A needs no floor of its own:
+// max(0, max(0, d), E, F) = max(d, E, F) for E, F >= 0.  The end-cell key stays the true key: h' * 4 + (31 - M - 4 A), wrapping per half, the addends in scalar
+// registers.  The scratch keeps un-offset values (store_to_scratch subtracts A, seed_from_scratch adds it): the tracebacks and the second fill read it.
+// -> A, or 0 where none fits: the largest H' + profile byte must stay below 0x7c00 as the keys do (a key3 batch: scores <= 990).
+VGK_HD uint32_t gssw_row_offset(uint32_t scale, uint32_t go, uint32_t ge, uint32_t bias) {      // (go, ge, bias scaled)
+    uint32_t a = go > ge ? go : ge; a = bias > a ? bias : a;
+    return scale * 990u + a + 255u < 0x7c00u ? a : 0u;
+}
+//   VGK_DIAG_ADD3  (offset rows) the diagonal candidate H' + s - bias as one three-input add of the negated bias instead of an add and a subtract
+#ifndef VGK_DIAG_ADD3
+#define VGK_DIAG_ADD3 1
+#endif
+// H' + s - bias of the offset rows, per half without carry or borrow (the host bodies check it).  nb = the bias, NEGATED under VGK_DIAG_ADD3: one v_add3_u32.
+VGK_HD uint32_t diag_unbias(uint32_t d, uint32_t sb, uint32_t nb) {
+#if VGK_DIAG_ADD3
+    (void)pk_sub_nb(pk_add_nc(d, sb), 0u - nb);
+    return d + sb + nb;
+#else
+    return pk_sub_nb(pk_add_nc(d, sb), nb);
+#endif
+}
 // best-cell key of a row: score*32 + (31 - row_in_lane), so one packed max keeps
 // the best score and, on ties, the smallest row (scores stay below 2047).
 constexpr uint32_t KEY_SHIFT = 5, KEY_LOW = 31;
@@ -406,14 +437,16 @@ constexpr uint32_t KEY_SHIFT = 5, KEY_LOW = 31;
 // an N in the graph (rare): the profile permute cannot express score 0, patch it.
 // max(0, diagonal + s) of row M, d = H of the row above in the previous column (the sum stays far below 2^16 per half).  With the tagged
 // candidates of the x8 traceback build the constant absorbs the diagonal's tag.
+// ofs (offset rows, lane_row): d and the result carry the offset and the result is not floored; bias2 then comes NEGATED under VGK_DIAG_ADD3.
 template <int K, int M, bool REFN, bool S8, bool TB>
-VGK_HD uint32_t row_diag(const Lane<K>& s, const GsswParams& P, uint32_t sel, uint32_t bias2, bool nA, bool nB, uint32_t d) {
+VGK_HD uint32_t row_diag(const Lane<K>& s, const GsswParams& P, uint32_t sel, uint32_t bias2, bool nA, bool nB, uint32_t d, bool ofs) {
     uint32_t sb = byte_perm(s.pb(M), s.PA[M], sel);
     if (REFN) {
         const uint32_t row = s.g * K + M;
         if (nA) sb = set_lo(sb, row < s.LA ? P.bias + row_bonus(s.bsA, s.beA, row, s.LA) : 0u);
         if (nB) sb = set_hi(sb, row < s.LB ? P.bias + row_bonus(s.bsB, s.beB, row, s.LB) : 0u);
     }
+    if (ofs) return diag_unbias(d, sb, bias2);
     return pk_subs(pk_add_nc(d, sb), (TB && S8) ? bias2 - 0x00040004u : bias2);
 }
 // `d` comes in as THIS row's diagonal candidate (row_diag) and leaves as the next row's, made from this row's old H before the new one is
@@ -421,9 +454,24 @@ VGK_HD uint32_t row_diag(const Lane<K>& s, const GsswParams& P, uint32_t sel, ui
 // copy per row (the rotation "new H[M] lives where old H[M - 1] did" cost K - 1 v_mov_b32 per step: 18 of ~290 VALU instructions).
 template <int K, int M, bool REFN, bool S8, bool TB, bool K3, bool NK>
 VGK_HD void lane_row(Lane<K>& s, const GsswParams& P, uint32_t sel, uint32_t bias2, uint32_t go2, uint32_t ge2,
-                     bool nA, bool nB, uint32_t& f, uint32_t& d, uint32_t* acc, uint32_t& ck) {
+                     bool nA, bool nB, uint32_t& f, uint32_t& d, uint32_t* acc, uint32_t& ck, bool ofs) {
     const uint32_t t4 = d;
-    if constexpr (M + 1 < K) d = row_diag<K, M + 1, REFN, S8, TB>(s, P, sel, bias2, nA, nB, s.H[M]);
+    if constexpr (M + 1 < K) d = row_diag<K, M + 1, REFN, S8, TB>(s, P, sel, bias2, nA, nB, s.H[M], ofs);
+    if constexpr (!TB && S8 && K3) {
+        if (ofs) {
+            // The offset form (gssw_row_offset): t4, E, F and H all carry A; the subtractions cannot borrow, the floor is the maxima's third input.
+            const uint32_t floor2 = rep2(P.row_off);
+            const uint32_t e = s.E[M];
+            const uint32_t h = pk_max3_f16(t4, e, f);
+            const uint32_t gg = pk_sub_nb(h, go2);
+            const uint32_t en = pk_max3_f16_u(gg, pk_sub_nb(e, ge2), floor2), fn = pk_max3_f16_u(gg, pk_sub_nb(f, ge2), floor2);
+            const uint32_t key = pk_mul_imm_add_u<1 << (KEY_SHIFT - 3)>(h, rep2((uint32_t)((int)KEY_LOW - M) - (P.row_off << (KEY_SHIFT - 3))));
+            if constexpr ((M & 1) == 0) { if constexpr (M + 1 < K) acc[0] = key; else ck = M == 0 ? key : pk_max(ck, key); }
+            else ck = M == 1 ? pk_max(acc[0], key) : pk_max3_f16(ck, acc[0], key);
+            s.H[M] = h; s.E[M] = en; f = fn;
+            return;
+        }
+    }
     if constexpr (!TB) {
         // The recurrence alone (TB_REWALK fills): no tags, no codes.  Its H / E / F are the tagged build's with the three tag bits
         // stripped — the tags are below the x8 scale's resolution and every constant that absorbs one is a multiple of 8 away from the
@@ -489,24 +537,25 @@ VGK_HD void lane_row(Lane<K>& s, const GsswParams& P, uint32_t sel, uint32_t bia
 
 template <int K, int M, bool REFN, bool S8, bool TB, bool K3, bool NK>
 VGK_HD void lane_rows_from(Lane<K>& s, const GsswParams& P, uint32_t sel, uint32_t bias2, uint32_t go2, uint32_t ge2,
-                           bool nA, bool nB, uint32_t& f, uint32_t& d, uint32_t* acc, uint32_t& ck) {
-    lane_row<K, M, REFN, S8, TB, K3, NK>(s, P, sel, bias2, go2, ge2, nA, nB, f, d, acc, ck);
-    if constexpr (M + 1 < K) lane_rows_from<K, M + 1, REFN, S8, TB, K3, NK>(s, P, sel, bias2, go2, ge2, nA, nB, f, d, acc, ck);
+                           bool nA, bool nB, uint32_t& f, uint32_t& d, uint32_t* acc, uint32_t& ck, bool ofs) {
+    lane_row<K, M, REFN, S8, TB, K3, NK>(s, P, sel, bias2, go2, ge2, nA, nB, f, d, acc, ck, ofs);
+    if constexpr (M + 1 < K) lane_rows_from<K, M + 1, REFN, S8, TB, K3, NK>(s, P, sel, bias2, go2, ge2, nA, nB, f, d, acc, ck, ofs);
 }
 
 // The K rows of one lane for one column; returns the K/4 traceback dwords and the column key maximum.
 template <int K, bool REFN, bool S8, bool TB, bool K3, bool NK>
 VGK_HD void lane_rows(Lane<K>& s, const GsswParams& P, uint32_t sel, uint32_t diag0, uint32_t rf,
-                      bool nA, bool nB, uint32_t* acc, uint32_t& colkey) {
+                      bool nA, bool nB, uint32_t* acc, uint32_t& colkey, bool ofs) {
     uint32_t bias2 = rep2(P.bias), go2 = rep2(P.go), ge2 = rep2(P.ge);
+    if (ofs && VGK_DIAG_ADD3) bias2 = 0u - bias2;
 #if defined(__HIP_DEVICE_COMPILE__)
     // The rare N variant must stay a separate branch: with opaque copies of its inputs the
     // optimiser cannot hoist "common" permutes/subtracts of all rows above the branch
     // (that hoisting cost 32 live VGPRs and spilled the hot loop).
     if (REFN) asm volatile("" : "+v"(sel), "+v"(bias2), "+v"(go2), "+v"(ge2));
 #endif
-    uint32_t f = rf, d = row_diag<K, 0, REFN, S8, TB>(s, P, sel, bias2, nA, nB, diag0), ck = 0;
-    lane_rows_from<K, 0, REFN, S8, TB, K3, NK>(s, P, sel, bias2, go2, ge2, nA, nB, f, d, acc, ck);
+    uint32_t f = rf, d = row_diag<K, 0, REFN, S8, TB>(s, P, sel, bias2, nA, nB, diag0, ofs), ck = 0;
+    lane_rows_from<K, 0, REFN, S8, TB, K3, NK>(s, P, sel, bias2, go2, ge2, nA, nB, f, d, acc, ck, ofs);
     s.out_h = s.H[K - 1]; s.out_f = f;
     colkey = ck;
 }
@@ -517,8 +566,14 @@ VGK_HD void lane_rows(Lane<K>& s, const GsswParams& P, uint32_t sel, uint32_t di
 // window (no end-cell tracking, no scratch stores: the fill has done both).
 // AV: every lane of the wavefront has a column of both its reads at this step (the steady middle of a fill: steps G - 1 .. the shortest window's
 // end) — nothing is tested for being there.
-template <int K, bool S8, bool TB, bool RE, bool K3 = false, bool NK = false, bool AV = false>
+// OFS: the offset form of the rows (gssw_row_offset; K3 && !TB fills only) — 1 / 0: on / off (the kernels say which at compile time), -1: on where
+// GsswParams::row_off is set (the emulator, which has one handle per K3).
+template <bool S8, bool TB, bool K3, int OFS>
+VGK_HD bool offset_rows(const GsswParams& P) { return S8 && !TB && K3 && (OFS > 0 || (OFS < 0 && P.row_off != 0u)); }
+template <int K, bool S8, bool TB, bool RE, bool K3 = false, bool NK = false, bool AV = false, int OFS = -1>
 VGK_HD void lane_column(Lane<K>& s, const GsswParams& P, uint32_t t, uint32_t rh, uint32_t rf, uint32_t rinfo, uint32_t* tb_a, uint32_t* tb_b) {
+    const bool ofs = offset_rows<S8, TB, K3, OFS>(P);
+    const uint32_t floor2 = ofs ? rep2(P.row_off) : 0u;
     s.info = rinfo;
     const uint32_t ia = rinfo & 0xffu, ib = (rinfo >> 16) & 0xffu;
     const bool vA = AV || !(ia & CI_INVALID), vB = AV || !(ib & CI_INVALID);
@@ -527,15 +582,15 @@ VGK_HD void lane_column(Lane<K>& s, const GsswParams& P, uint32_t t, uint32_t rh
         if (vA && (ia & CI_NODE_START)) s.nodeA += 1;
         if (vB && (ib & CI_NODE_START)) s.nodeB += 1;
         if (rinfo & (CI_SEED_SLOW * 0x00010001u)) {                                // (one test for the pair: a column that is not there carries no flag)
-            if (vA && (ia & CI_SEED_SLOW)) seed_from_scratch<0, K>(s, P, s.probA, s.nodeA, diag0);
-            if (vB && (ib & CI_SEED_SLOW)) seed_from_scratch<1, K>(s, P, s.probB, s.nodeB, diag0);
+            if (vA && (ia & CI_SEED_SLOW)) seed_from_scratch<0, K>(s, P, s.probA, s.nodeA, diag0, floor2);
+            if (vB && (ib & CI_SEED_SLOW)) seed_from_scratch<1, K>(s, P, s.probB, s.nodeB, diag0, floor2);
         }
         // selector: byte0 <- PA[baseA], byte2 <- PB[baseB] (bytes 4..7 of the permute), bytes 1,3 <- 0
         const uint32_t sel = (rinfo & 0x00030003u) | 0x0c040c00u;
         uint32_t acc[(K + 3) / 4], colkey;
         // (an N is base code 4, the only code with bit 2 set; a column that is not there reads CI_INVALID, whose base bits are 0)
-        if (rinfo & 0x00040004u) { const bool nA = (ia & CI_BASE_MASK) == 4, nB = (ib & CI_BASE_MASK) == 4; lane_rows<K, true, S8, TB, K3, NK>(s, P, sel, diag0, rf, nA, nB, acc, colkey); }
-        else          lane_rows<K, false, S8, TB, K3, NK>(s, P, sel, diag0, rf, false, false, acc, colkey);
+        if (rinfo & 0x00040004u) { const bool nA = (ia & CI_BASE_MASK) == 4, nB = (ib & CI_BASE_MASK) == 4; lane_rows<K, true, S8, TB, K3, NK>(s, P, sel, diag0, rf, nA, nB, acc, colkey, ofs); }
+        else          lane_rows<K, false, S8, TB, K3, NK>(s, P, sel, diag0, rf, false, false, acc, colkey, ofs);
         if constexpr (TB) {
             if (tb_a) {
                 if (TB_TILE > 1 && !RE) {                                          // part A is a 16-byte slot: one store
@@ -558,12 +613,12 @@ VGK_HD void lane_column(Lane<K>& s, const GsswParams& P, uint32_t t, uint32_t rh
             s.best_hi = upB ? khi : s.best_hi; s.step_hi = upB ? t : s.step_hi;
             }
             if (rinfo & (CI_STORE_END * 0x00010001u)) {
-                if (vA && (ia & CI_STORE_END)) store_to_scratch<0, K>(s, P, s.probA, s.nodeA);
-                if (vB && (ib & CI_STORE_END)) store_to_scratch<1, K>(s, P, s.probB, s.nodeB);
+                if (vA && (ia & CI_STORE_END)) store_to_scratch<0, K>(s, P, s.probA, s.nodeA, floor2);
+                if (vB && (ib & CI_STORE_END)) store_to_scratch<1, K>(s, P, s.probB, s.nodeB, floor2);
             }
         }
     } else {
-        s.out_h = 0; s.out_f = 0;
+        s.out_h = floor2; s.out_f = floor2;
     }
     s.prev_rh = rh;
 }
@@ -575,10 +630,10 @@ VGK_HD void steady_steps(uint32_t G, uint32_t shortest, uint32_t n_steps, uint32
 }
 // One step of one lane of the fill.  rh/rf/rinfo are lane-1's out_h/out_f/info from the
 // previous step (ignored by group leaders, which start a fresh column).
-template <int K, bool S8, bool TB = true, bool K3 = false, bool NK = false, bool AV = false>
+template <int K, bool S8, bool TB = true, bool K3 = false, bool NK = false, bool AV = false, int OFS = -1>
 VGK_HD void lane_step(Lane<K>& s, const GsswParams& P, uint32_t t, uint32_t rh, uint32_t rf, uint32_t rinfo, uint32_t* tb_a, uint32_t* tb_b) {
-    if (s.g == 0) { rh = 0; rf = 0; rinfo = fetch_info(s, P, t); }
-    lane_column<K, S8, TB, false, K3, NK, AV>(s, P, t, rh, rf, rinfo, tb_a, tb_b);
+    if (s.g == 0) { rh = rf = offset_rows<S8, TB, K3, OFS>(P) ? rep2(P.row_off) : 0u; rinfo = fetch_info(s, P, t); }
+    lane_column<K, S8, TB, false, K3, NK, AV, OFS>(s, P, t, rh, rf, rinfo, tb_a, tb_b);
 }
 
 // after the last step: publish this lane's best cell (LOCAL mode)
@@ -1152,7 +1207,7 @@ VGK_HD void band_fill_lane(const GsswParams& P, const WaveDesc& wd, uint32_t lan
 #if VGK_PB_LDS && defined(__HIPCC__)
     s.PBL = (typename Lane<K>::lds_u32*)(uintptr_t)0;      // (unsupported with VGK_PB_LDS)
 #endif
-    lane_init(s, P, wd, lane);                   // the pair, its rows' profiles, the lane block index g — as the fill began
+    lane_init<K, -1, 0>(s, P, wd, lane);         // the pair, its rows' profiles, the lane block index g — as the fill began
     const uint32_t g = s.g;
     uint32_t re[2] = {0, 0}, ce[2] = {0, 0}; TbBand bd[2]; bd[0].used = bd[1].used = false;
     const uint32_t prob[2] = {s.probA, s.probB};

@@ -479,12 +479,14 @@ int vgk_gssw_pack(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_t n, ui
     P.walk_passes = walk2 && !P.fused ? 2 : 1;                          // (local alignments with a traceback: what walk_diag_one serves)
     if (P.walk_passes != 2 || P.tb_mode != TB_CODES) P.spec_fill = 0;
     set_refill_bound(P, ctx);
-    P.key3 = 0;
+    P.key3 = 0; P.row_off = 0;
     if (P.spec_fill) {                                                  // the first fill's column key maximum by v_pk_maximum3_f16 (gssw_device.hpp, K3)
         uint32_t longest = 0; bool xdrop = false;
         for (uint32_t i = 0; i < n; ++i) { longest = std::max(longest, probs[i].L); xdrop = xdrop || (problems[i].flags & 15u) == (uint32_t)VGK_XDROP_PINNED; }
         P.key3 = gssw_key3_ok(S, ctx->has_qa, xdrop, longest, (uint32_t)std::max(0, ctx->max_score), (uint32_t)std::max(0, ctx->max_bonus)) && !std::getenv("VGAMD_NO_KEY3") ? 1u : 0u;
     }
+    // ... and its rows in the offset form where the scoring leaves room for the constant (gssw_row_offset)
+    P.row_off = P.key3 && !std::getenv("VGAMD_NO_OFFSET_ROWS") ? gssw_row_offset(S, P.go, P.ge, P.bias) : 0u;
     std::memcpy(P.matrix, ctx->sc.matrix, 25);
     b->ops_total = ops_total;
     if ((rc = ctx->be->sync_side())) return fail(rc);     // inputs are resident in HBM when pack returns (the uploads have their own stream)
@@ -782,6 +784,13 @@ extern "C" int vgk_batch_refill_stats(vgk_batch* b, uint64_t out[5]) try {
     for (uint32_t i : list) if (i < b->n && probs[i].col0) ++out[3];
     return VGK_OK;
 } catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }      // (no exception leaves the C ABI)
+// The constant (scaled) the rows of this batch's speculative first fill carry in the offset form (gssw_device.hpp: gssw_row_offset), 0 = the batch does not
+// speculate or its first fill runs the saturating rows (engine only, for tests and measurements; not part of include/vgk.h)
+extern "C" uint32_t vgk_batch_row_offset(vgk_batch* b) { return b && b->P.spec_fill && b->P.key3 ? b->P.row_off : 0u; }
+#if defined(VGK_PK_CHECK)
+// (the emulator's build) calls of pk_add_nc / pk_sub_nb so far whose operands carried or borrowed across the halves: must stay 0
+extern "C" uint64_t vgk_pk_check_failures(void) { return pk_check_failures.load(); }
+#endif
 int      vgk_batch_lane(vgk_batch* b) { return b ? b->lane : 0; }
 int      vgk_batch_speculated(vgk_batch* b) { if (!b) return 0; std::lock_guard<std::mutex> lk(b->ctx->mu); return b->ran && b->ran_spec ? 1 : 0; }
 int      vgk_set_speculation(vgk_ctx* ctx, int mode) {
