@@ -63,3 +63,9 @@ choose: tests/emu/libvgamd_choose.so
 tests/emu/libvgamd_choose.so: tests/emu/choose_driver.cpp $(LIB_HDRS)
 	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -shared -o $@ $<
 .PHONY: choose
+
+# test-only: the serial form of the chaining rule on the device (chain_items_device.hpp: ci_problem_one) behind one C call
+chainitems: tests/emu/libvgamd_chainitems.so
+tests/emu/libvgamd_chainitems.so: tests/emu/chain_items_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -shared -o $@ $<
+.PHONY: chainitems

@@ -77,6 +77,56 @@ int vgk_batch_refill_stats(vgk_batch* batch, uint64_t out[5]);
  * when the batch was packed). */
 uint32_t vgk_batch_row_offset(vgk_batch* batch);
 
+/* ---- chaining anchors on the device: algorithms::find_best_chains over given transitions ---------------------------------------------------
+ * The step between the seeds and the chain stage (src/algorithms/chain_items.cpp:735-877, called once per zip-code tree per read at
+ * src/minimizer_mapper_from_chains.cpp:1646): the DP chain_items_dp (:385-648) over the transitions add_transition_if_legal lets through
+ * (:270-355), the multi-chain traceback (:650-733) and the recombination positions of every chain (:793-868) — for thousands of (read, tree)
+ * problems per call.  No distance index is needed: what reaches the DP in the reference is a list of (from, to, graph distance) — that list is
+ * this call's input, in any order.  The rule is the host shim's find_best_chains (vg_amd/host/chain_items.cpp), result for result.
+ *
+ * A problem is its anchors in the order sort_anchor_indexes leaves them (read start ascending, read end descending) and its candidate
+ * transitions.  Problem p's anchors are anchors[anchor_off[p] .. anchor_off[p + 1]), its candidates candidates[cand_off[p] .. cand_off[p + 1]);
+ * `from` and `to` number the anchors within the problem.
+ *
+ * Out: problem p's chains are chains[chain_off[p] .. chain_off[p + 1]), best first (at least one: a problem without anchors, or max_chains 0,
+ * has the reference's one empty chain of score 0).  A chain's anchors, left to right, are items[item_begin .. item_begin + n_items); the anchors
+ * that introduce a recombination (rec_positions) are rec_right[rec_begin .. rec_begin + n_rec), the left boundaries of the backward pass
+ * rec_left[rec_begin .. rec_begin + n_rec_left), both in chain order — the reference's rec_intervals exist exactly when n_rec_left == n_rec.
+ * Room, all the caller's: chain_off n_problems + 1; chains the sum over the problems of max(1, min(anchors, max_chains)); items, rec_right,
+ * rec_left the number of anchors each (at least 1).  table_score / table_source (nullable, one entry per anchor): the DP table, source
+ * UINT32_MAX = from nowhere.
+ *
+ * Ties the reference leaves to std::sort are fixed here [PARITY-UNPINNED]: traceback starts by score descending, then source descending
+ * (nowhere largest), then anchor number ascending; chains by penalty ascending, then in order of creation.
+ *
+ * VGK_EINVAL: anchors out of order or of length 0; from / to outside the problem; a negative recombination_penalty or consistency_bonus; a
+ * gap_scale that is negative or not finite; offsets that do not ascend (or do not begin at 0).  VGK_EUNSUPPORTED: an indel limit above
+ * vgk_chain_items_limits' out[1]; a problem whose score sums could leave int32.  VGK_ETOOBIG: more than 2^32 - 16 anchors or candidates. */
+typedef struct vgk_chain_anchor {      /* 48 B; algorithms::Anchor without its positions and zip codes */
+    uint32_t read_start, length, margin_before, margin_after;
+    int32_t  score;  uint32_t start_hint_offset, end_hint_offset, base_seed_length;
+    uint64_t start_paths, end_paths;
+} vgk_chain_anchor;
+/* anchor numbers within the problem; the distance between the two hint points, as ZipCodeTree::find_distances reports it */
+typedef struct vgk_chain_candidate { uint32_t from, to, graph_distance; } vgk_chain_candidate;
+typedef struct vgk_chain_scheme {
+    int32_t item_bonus, recombination_penalty, consistency_bonus;  uint32_t max_chains;  double gap_scale;
+    uint32_t max_read_lookback_bases /* UINT32_MAX = none */, max_indel_bases;           /* used where the per-problem arrays are NULL */
+} vgk_chain_scheme;
+typedef struct vgk_chain_found { int32_t score; uint32_t item_begin, n_items, rec_begin, n_rec, n_rec_left; } vgk_chain_found;
+
+int vgk_chain_items(vgk_ctx* ctx, const vgk_chain_scheme* scheme, uint32_t n_problems,
+                    const uint64_t* anchor_off, const vgk_chain_anchor* anchors,
+                    const uint64_t* cand_off, const vgk_chain_candidate* candidates,
+                    const uint32_t* read_lookback /* [n], nullable */, const uint32_t* indel_limit /* [n], nullable */,
+                    uint64_t* chain_off /* [n + 1] */, vgk_chain_found* chains, uint32_t* items, uint32_t* rec_right, uint32_t* rec_left,
+                    int32_t* table_score /* nullable */, uint32_t* table_source /* nullable; UINT32_MAX = nowhere */);
+/* out[0] = anchors of a problem whose table fits LDS (larger problems run over a slab in HBM), out[1] = the largest indel limit the penalty
+ * tables take, out[2] = lanes per problem, out[3] = 0 (reserved).  Needs no context. */
+int vgk_chain_items_limits(uint32_t out[4]);
+/* Device time (ms) of the last vgk_chain_items call on this context: legality + grouping | DP | traceback */
+int vgk_chain_items_last_ms(vgk_ctx* ctx, double ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

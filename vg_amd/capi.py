@@ -78,6 +78,53 @@ def find_seeds_policy(P):
     return FindSeedsPolicy(int(P["hit_cap"]), int(P["hard_hit_cap"]), float(P["score_fraction"]), int(P["max_unique_min"]), int(P["num_bp_per_min"]), int(P["coverage_flank"]),
                            int(bool(P["exclude_overlapping_min"])), int(P["window_count"]), 0, min(int(P["max_window_length"]), (1 << 64) - 1))
 
+# vgk_chain_items (include/vgk_engine.h): anchors, candidate transitions and the chains found
+CHAIN_ANCHOR_DT = np.dtype([("read_start", "<u4"), ("length", "<u4"), ("margin_before", "<u4"), ("margin_after", "<u4"), ("score", "<i4"), ("start_hint_offset", "<u4"),
+                            ("end_hint_offset", "<u4"), ("base_seed_length", "<u4"), ("start_paths", "<u8"), ("end_paths", "<u8")])
+CHAIN_CANDIDATE_DT = np.dtype([("from", "<u4"), ("to", "<u4"), ("graph_distance", "<u4")])
+CHAIN_FOUND_DT = np.dtype([("score", "<i4"), ("item_begin", "<u4"), ("n_items", "<u4"), ("rec_begin", "<u4"), ("n_rec", "<u4"), ("n_rec_left", "<u4")])
+CHAIN_NOWHERE = 0xffffffff
+# ChainScoringScheme's defaults (src/algorithms/chain_items.hpp:407-418), one chain, no read lookback, find_best_chain's indel limit of 100
+CHAIN_SCHEME_DEFAULTS = dict(item_bonus=0, recombination_penalty=0, consistency_bonus=0, max_chains=1, gap_scale=1.0, max_read_lookback_bases=0xffffffff, max_indel_bases=100)
+
+
+class ChainScheme(ctypes.Structure):           # vgk_chain_scheme
+    _fields_ = [("item_bonus", ctypes.c_int32), ("recombination_penalty", ctypes.c_int32), ("consistency_bonus", ctypes.c_int32), ("max_chains", ctypes.c_uint32),
+                ("gap_scale", ctypes.c_double), ("max_read_lookback_bases", ctypes.c_uint32), ("max_indel_bases", ctypes.c_uint32)]
+
+
+def chain_scheme(S=None):
+    """a scheme in the keys of CHAIN_SCHEME_DEFAULTS (missing ones: the defaults) -> ChainScheme"""
+    S = dict(CHAIN_SCHEME_DEFAULTS, **(S or {}))
+    return ChainScheme(int(S["item_bonus"]), int(S["recombination_penalty"]), int(S["consistency_bonus"]), int(S["max_chains"]), float(S["gap_scale"]),
+                       int(S["max_read_lookback_bases"]), int(S["max_indel_bases"]))
+
+
+def chain_items_call(fn, head, scheme, anchor_off, anchors, cand_off, candidates, read_lookback=None, indel_limit=None, tail=()):
+    """one call with vgk_chain_items' arguments (the engine's, the host shim's vgh_find_best_chains, the serial lane code's): head / tail = what the
+    function takes before the scheme / behind table_source -> (rc, dict(chain_off, chains, items, rec_right, rec_left, table_score, table_source))"""
+    aoff = np.ascontiguousarray(anchor_off, dtype=np.uint64); coff = np.ascontiguousarray(cand_off, dtype=np.uint64); n = len(aoff) - 1
+    anchors = np.ascontiguousarray(anchors, dtype=CHAIN_ANCHOR_DT); candidates = np.ascontiguousarray(candidates, dtype=CHAIN_CANDIDATE_DT)
+    sch = scheme if isinstance(scheme, ChainScheme) else chain_scheme(scheme)
+    look = None if read_lookback is None else np.ascontiguousarray(read_lookback, dtype=np.uint32); lim = None if indel_limit is None else np.ascontiguousarray(indel_limit, dtype=np.uint32)
+    sizes = np.diff(aoff.astype(np.int64)) if n else np.zeros(0, dtype=np.int64)
+    room = int(np.maximum(1, np.minimum(sizes, sch.max_chains)).sum()) if n else 0
+    out = dict(chain_off=np.zeros(n + 1, dtype=np.uint64), chains=np.zeros(max(room, 1), dtype=CHAIN_FOUND_DT))
+    for name in ("items", "rec_right", "rec_left", "table_source"):
+        out[name] = np.zeros(max(len(anchors), 1), dtype=np.uint32)
+    out["table_score"] = np.zeros(max(len(anchors), 1), dtype=np.int32)
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p] * len(head) + [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 13 + [type(t) for t in tail]
+    rc = fn(*head, ctypes.byref(sch), n, aoff.ctypes.data, anchors.ctypes.data if len(anchors) else None, coff.ctypes.data, candidates.ctypes.data if len(candidates) else None,
+            None if look is None else look.ctypes.data, None if lim is None else lim.ctypes.data, out["chain_off"].ctypes.data, out["chains"].ctypes.data,
+            out["items"].ctypes.data, out["rec_right"].ctypes.data, out["rec_left"].ctypes.data, out["table_score"].ctypes.data, out["table_source"].ctypes.data, *tail)
+    if rc == VGK_OK:
+        out["chains"] = out["chains"][:int(out["chain_off"][-1])]
+        for name in ("items", "rec_right", "rec_left", "table_source", "table_score"):
+            out[name] = out[name][:len(anchors)]
+    return rc, out
+
+
 MINIMIZER_REVERSE = 1
 # vgk_chain_stitch (include/vgk.h): pieces of a read's chain in, one composed alignment per read out
 CHAIN_PIECE_DT = np.dtype([("kind", "<u4"), ("link", "<u4"), ("node_offset", "<u4"), ("path_begin", "<u4"), ("path_len", "<u4"), ("edit_begin", "<u4"), ("n_edits", "<u4"), ("reserved", "<u4")])
@@ -625,6 +672,27 @@ class Engine:
     def minimizer_choose_last_ms(self):
         self.lib.vgk_minimizer_choose_last_ms.restype = ctypes.c_double; self.lib.vgk_minimizer_choose_last_ms.argtypes = [ctypes.c_void_p]
         return self.lib.vgk_minimizer_choose_last_ms(self.h)
+
+    def chain_items(self, scheme, anchor_off, anchors, cand_off, candidates, read_lookback=None, indel_limit=None):
+        """vgk_chain_items (include/vgk_engine.h): find_best_chains on the device for a batch of (read, tree) problems.  scheme: the keys of
+        CHAIN_SCHEME_DEFAULTS; anchors CHAIN_ANCHOR_DT in sort_anchor_indexes' order per problem; candidates CHAIN_CANDIDATE_DT in any order.
+        -> dict(chain_off [n + 1], chains CHAIN_FOUND_DT, items, rec_right, rec_left, table_score, table_source (CHAIN_NOWHERE = from nowhere))"""
+        rc, out = chain_items_call(self.lib.vgk_chain_items, (self.h,), scheme, anchor_off, anchors, cand_off, candidates, read_lookback, indel_limit)
+        self._check(rc, "vgk_chain_items")
+        return out
+
+    def chain_items_limits(self):
+        """-> (anchors of a problem whose table fits LDS, the largest indel limit, lanes per problem, 0)"""
+        out = (ctypes.c_uint32 * 4)()
+        self._check(self.lib.vgk_chain_items_limits(out), "vgk_chain_items_limits")
+        return tuple(int(x) for x in out)
+
+    def chain_items_last_ms(self):
+        """device time of the last chain_items call: (legality + grouping, DP, traceback) in ms"""
+        ms = (ctypes.c_double * 3)()
+        self.lib.vgk_chain_items_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_chain_items_last_ms(self.h, ms), "vgk_chain_items_last_ms")
+        return tuple(float(x) for x in ms)
 
     def minimizer_last_ms(self):
         self.lib.vgk_minimizer_last_ms.restype = ctypes.c_double; self.lib.vgk_minimizer_last_ms.argtypes = [ctypes.c_void_p]

@@ -1027,6 +1027,160 @@ __global__ void __launch_bounds__(64) minimizer_choose_slab_kernel(const MzChoos
     W.hits = (uint32_t*)s; s += 4 * np; W.run_hits = (uint32_t*)s; s += 4 * np; W.start = (uint32_t*)s; s += 4 * np; W.perm = (uint32_t*)s; s += 4 * np; W.off = (uint32_t*)s; s += 4 * np; W.dq = (uint32_t*)s;
     for (uint32_t i = blockIdx.x; i < P.n; i += gridDim.x) { choose_read<ChooseSlab>(P, P.ids[i], W, threadIdx.x); __syncthreads(); }
 }
+// ---- chains of anchors (chain_items_device.hpp: ci_problem_one is the rule and the checker).  A lane per candidate transition applies the filter
+// and counts its destination's group; after the prefix sums a lane per survivor claims a place in that group (an atomic: the order inside a group
+// is free, the winner is a maximum) and leaves (from, jump) there, the jump looked up here, off the DP's serial path.
+__global__ void __launch_bounds__(256) chain_items_legal_kernel(const CiParams P) {
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= P.n_cands) return;
+    const CiProb q = P.probs[ci_problem_of(P.cand_off, P.n_problems, c)];
+    const vgk_chain_candidate e = P.cands[c];
+    uint32_t indel = CI_DROPPED, why = 0;
+    if (e.from >= q.n || e.to >= q.n) atomicOr(P.flags, 1u);
+    else indel = ci_legal(P.anchors[q.a_off + e.from], P.anchors[q.a_off + e.to], e.graph_distance, q.lookback, q.limit, &why);
+    P.indel[c] = indel;
+    if (indel != CI_DROPPED) atomicAdd(&P.count[q.a_off + e.to], 1u);
+}
+__global__ void __launch_bounds__(256) chain_items_scatter_kernel(const CiParams P) {
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= P.n_cands) return;
+    const uint32_t indel = P.indel[c];
+    if (indel == CI_DROPPED) return;
+    const CiProb q = P.probs[ci_problem_of(P.cand_off, P.n_problems, c)];
+    const vgk_chain_candidate e = P.cands[c];
+    const uint64_t dest = q.a_off + e.to;
+    const uint32_t pos = P.first[dest] + atomicAdd(&P.cursor[dest], 1u);
+    P.grouped[pos] = CiEdge{e.from, P.jump[q.jump_off + indel]};
+}
+// The DP: one wavefront per problem, destinations in anchor order.  The next 64 destinations sit one in each lane's registers (points, paths, the
+// bounds of their groups) and are broadcast as their turn comes; the lanes stride over a destination's group — its first 64 transitions are
+// fetched while the destination before it is reduced —, the three-part key is reduced across the wave by shuffles, and lane 0 writes the entry.
+__device__ inline uint32_t ci_bc(uint32_t v, uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j); }
+__device__ inline uint64_t ci_bc(uint64_t v, uint32_t j) { return ((uint64_t)ci_bc((uint32_t)(v >> 32), j) << 32) | ci_bc((uint32_t)v, j); }
+__device__ void ci_dp_problem(const CiParams& P, uint32_t p, int32_t* sc, uint64_t* paths, uint32_t lane) {
+    const CiProb q = P.probs[p]; const uint32_t n = q.n;
+    const vgk_chain_anchor* a = P.anchors + q.a_off; const uint32_t* first = P.first + q.a_off;
+    const int32_t rp = P.recombination_penalty, cb = P.consistency_bonus;
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t i = base + lane;
+        int32_t my_points = 0; uint64_t my_start = 0, my_end = 0; uint32_t my_g0 = 0, my_g1 = 0;
+        if (i < n) { const vgk_chain_anchor x = a[i]; my_points = x.score + P.item_bonus; my_start = x.start_paths; my_end = x.end_paths; my_g0 = first[i]; my_g1 = first[i + 1]; }
+        const uint32_t cnt = n - base < 64u ? n - base : 64u;
+        CiEdge ahead{0u, 0};
+        { const uint32_t b0 = ci_bc(my_g0, 0), b1 = ci_bc(my_g1, 0); if (b0 + lane < b1) ahead = P.grouped[b0 + lane]; }
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint32_t t = base + j;
+            const int32_t points = (int32_t)ci_bc((uint32_t)my_points, j); const uint64_t start = ci_bc(my_start, j), end = ci_bc(my_end, j);
+            const uint32_t b0 = ci_bc(my_g0, j), b1 = ci_bc(my_g1, j);
+            const CiEdge cur = ahead;
+            if (j + 1 < cnt) { const uint32_t nb0 = ci_bc(my_g0, j + 1), nb1 = ci_bc(my_g1, j + 1); if (nb0 + lane < nb1) ahead = P.grouped[nb0 + lane]; }
+            CiKey best = ci_from_nowhere(points, cb);
+            if (b0 + lane < b1) {
+                const CiKey k = ci_candidate(sc[cur.from], paths[cur.from], cur.from, cur.jump, points, start, end, rp, cb);
+                if (ci_key_greater(k, best)) best = k;
+            }
+            for (uint32_t g = b0 + 64u + lane; g < b1; g += 64u) {
+                const CiEdge e = P.grouped[g];
+                const CiKey k = ci_candidate(sc[e.from], paths[e.from], e.from, e.jump, points, start, end, rp, cb);
+                if (ci_key_greater(k, best)) best = k;
+            }
+            uint32_t k0 = (uint32_t)best.eval ^ 0x80000000u, k1 = (uint32_t)best.score ^ 0x80000000u, k2 = best.source;
+            for (int d = 32; d > 0; d >>= 1) {
+                const uint32_t o0 = __shfl_xor(k0, d), o1 = __shfl_xor(k1, d), o2 = __shfl_xor(k2, d);
+                if (o0 > k0 || (o0 == k0 && (o1 > k1 || (o1 == k1 && o2 > k2)))) { k0 = o0; k1 = o1; k2 = o2; }
+            }
+            const int32_t score = (int32_t)(k1 ^ 0x80000000u); const uint32_t source = k2;
+            const uint64_t kept = source == CI_NOWHERE ? end : ci_paths_after(paths[source], start, end);
+            if (lane == 0) { sc[t] = score; paths[t] = kept; P.t_score[q.a_off + t] = score; P.t_source[q.a_off + t] = source; }
+            __syncthreads();
+        }
+    }
+}
+extern __shared__ uint64_t ci_lds[];
+__global__ void __launch_bounds__(64) chain_items_dp_kernel(const CiParams P) {
+    ci_dp_problem(P, P.ids[blockIdx.x], (int32_t*)(ci_lds + P.lds_np), ci_lds, threadIdx.x);
+}
+__global__ void __launch_bounds__(64) chain_items_dp_slab_kernel(const CiParams P) {
+    char* s = P.slab + (uint64_t)blockIdx.x * P.slab_stride;
+    for (uint32_t i = blockIdx.x; i < P.n; i += gridDim.x) { ci_dp_problem(P, P.ids[i], (int32_t*)(s + 8ull * P.slab_n), (uint64_t*)s, threadIdx.x); __syncthreads(); }
+}
+// The tracebacks: the same wavefront shape.  The starts are put in order by a bitonic sort of anchor numbers (ci_start_before over the table), lane 0
+// walks them (every anchor is visited once), the tracebacks are sorted by penalty the same way, and a lane per chain writes it out with its two
+// recombination passes.
+template <class IDX> struct CiTraceWork { int32_t* score; uint32_t* source; int32_t* pen; uint32_t* used; IDX* order; IDX* tmp; IDX* obeg; IDX* begin; };
+template <class IDX, class BEFORE> __device__ void ci_bitonic(IDX* order, uint32_t np, uint32_t lane, BEFORE before) {
+    constexpr IDX PAD = (IDX)~(IDX)0;
+    for (uint32_t kk = 2; kk <= np; kk <<= 1) for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
+        for (uint32_t t = lane; t < np / 2; t += 64) {
+            const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i | j;
+            const IDX oi = order[i], ol = order[l];
+            const bool l_first = ol != PAD && (oi == PAD || before((uint32_t)ol, (uint32_t)oi));
+            if (l_first == ((i & kk) == 0)) { order[i] = ol; order[l] = oi; }
+        }
+        __syncthreads();
+    }
+}
+template <class IDX, bool COPY> __device__ void ci_trace_problem(const CiParams& P, uint32_t p, const CiTraceWork<IDX>& W, uint32_t lane) {
+    constexpr IDX PAD = (IDX)~(IDX)0;
+    const CiProb q = P.probs[p]; const uint32_t n = q.n, base = (uint32_t)q.a_off;
+    const vgk_chain_anchor* a = P.anchors + q.a_off; vgk_chain_found* out = P.chains + q.slot;
+    if (!n || !P.max_chains) { if (lane == 0) { out[0] = vgk_chain_found{0, base, 0u, base, 0u, 0u}; P.n_chains[p] = 1u; } return; }
+    uint32_t np = 1; while (np < n) np <<= 1;
+    int32_t best = (int32_t)0x80000000;
+    for (uint32_t i = lane; i < np; i += 64) {
+        if (i < n) {
+            const int32_t s = P.t_score[q.a_off + i];
+            if (COPY) { W.score[i] = s; W.source[i] = P.t_source[q.a_off + i]; }
+            best = s > best ? s : best; W.order[i] = (IDX)i;
+        } else W.order[i] = PAD;
+    }
+    for (uint32_t w = lane; w < (n + 31u) / 32u; w += 64) W.used[w] = 0u;
+    for (int d = 32; d > 0; d >>= 1) { const int32_t o = __shfl_xor(best, d); best = o > best ? o : best; }
+    __syncthreads();
+    ci_bitonic<IDX>(W.order, np, lane, [&](uint32_t x, uint32_t y) { return ci_start_before(W.score[x], W.source[x], x, W.score[y], W.source[y], y); });
+    uint32_t n_tb = 0;
+    if (lane == 0) n_tb = ci_walk<IDX>(n, W.order, W.score, W.source, a, P.item_bonus, best, W.used, W.tmp, W.pen, W.begin);
+    n_tb = (uint32_t)__shfl((int)n_tb, 0);
+    __syncthreads();
+    uint32_t np2 = 1; while (np2 < n_tb) np2 <<= 1;
+    for (uint32_t k = lane; k < np2; k += 64) W.order[k] = k < n_tb ? (IDX)k : PAD;
+    __syncthreads();
+    ci_bitonic<IDX>(W.order, np2, lane, [&](uint32_t x, uint32_t y) { return W.pen[x] < W.pen[y] || (W.pen[x] == W.pen[y] && x < y); });
+    const uint32_t n_out = n_tb < P.max_chains ? n_tb : P.max_chains;
+    if (lane == 0) {
+        uint32_t at = 0;
+        for (uint32_t k = 0; k < n_out; ++k) { const uint32_t tb = W.order[k]; W.obeg[k] = (IDX)at; at += (uint32_t)W.begin[tb + 1] - (uint32_t)W.begin[tb]; }
+        P.n_chains[p] = n_out;
+    }
+    __syncthreads();
+    for (uint32_t k = lane; k < n_out; k += 64) {
+        const uint32_t tb = W.order[k], b = W.begin[tb], len = (uint32_t)W.begin[tb + 1] - b, at = base + (uint32_t)W.obeg[k];
+        for (uint32_t i = 0; i < len; ++i) P.items[at + i] = W.tmp[b + len - 1u - i];
+        uint32_t nr = 0, nl = 0;
+        ci_rec_passes(a, P.items + at, len, P.rec_right + at, P.rec_left + at, &nr, &nl);
+        out[k] = vgk_chain_found{best - W.pen[tb], at, len, at, nr, nl};
+    }
+}
+__global__ void __launch_bounds__(64) chain_items_trace_kernel(const CiParams P) {
+    const uint32_t np = P.lds_np;
+    CiTraceWork<uint16_t> W;
+    uint32_t* w = (uint32_t*)ci_lds;
+    W.score = (int32_t*)w; w += np; W.source = w; w += np; W.pen = (int32_t*)w; w += np; W.used = w; w += np / 32u + 1u;
+    uint16_t* h = (uint16_t*)w;
+    W.order = h; h += np; W.tmp = h; h += np; W.obeg = h; h += np; W.begin = h;      // (begin: np + 2 entries)
+    ci_trace_problem<uint16_t, true>(P, P.ids[blockIdx.x], W, threadIdx.x);
+}
+__global__ void __launch_bounds__(64) chain_items_trace_slab_kernel(const CiParams P) {
+    uint32_t* w = (uint32_t*)(P.slab + (uint64_t)blockIdx.x * P.slab_stride);
+    CiTraceWork<uint32_t> W;
+    W.pen = (int32_t*)w; w += P.slab_n; W.used = w; w += P.slab_n / 32u + 1u; W.order = w; w += P.slab_np; W.tmp = w; w += P.slab_n; W.obeg = w; w += P.slab_n; W.begin = w;      // (begin: slab_n + 2 entries)
+    for (uint32_t i = blockIdx.x; i < P.n; i += gridDim.x) {
+        const uint32_t p = P.ids[i];
+        W.score = P.t_score + P.probs[p].a_off; W.source = P.t_source + P.probs[p].a_off;      // the table where the DP left it
+        ci_trace_problem<uint32_t, false>(P, p, W, threadIdx.x);
+        __syncthreads();
+    }
+}
 // ---- one Path per read (chain_device.hpp): a lane per read for the bounds and the composition, a wavefront per read for the dense copy
 __global__ void __launch_bounds__(64) chain_stitch_kernel(const CsParams P, const int what) {
     cs_one(P, what, blockIdx.x * 64 + threadIdx.x);
@@ -1847,6 +2001,26 @@ public:
     int run_minimizer_seeds_of(const MzSeedsOfParams& p) override {
         hipSetDevice(dev);
         hipLaunchKernelGGL(minimizer_seeds_of_kernel, dim3((p.n + 256) / 256), dim3(256), 0, stream, p);
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_chain_items(const CiParams& p, int what, uint32_t blocks) override {
+        hipSetDevice(dev);
+        if (what == CI_RUN_LEGAL || what == CI_RUN_SCATTER) {
+            if (!p.n_cands) return VGK_OK;
+            const dim3 grid((uint32_t)((p.n_cands + 255) / 256));
+            if (what == CI_RUN_LEGAL) hipLaunchKernelGGL(chain_items_legal_kernel, grid, dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL(chain_items_scatter_kernel, grid, dim3(256), 0, stream, p);
+        } else {
+            if (!blocks) return VGK_OK;
+            if (!p.slab && (p.lds_np > CI_LDS_MAX || (p.lds_np & (p.lds_np - 1u)))) return VGK_EINVAL;
+            if (what == CI_RUN_DP) {
+                if (p.slab) hipLaunchKernelGGL(chain_items_dp_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
+                else hipLaunchKernelGGL(chain_items_dp_kernel, dim3(blocks), dim3(64), ci_dp_lds_bytes(p.lds_np), stream, p);
+            } else if (what == CI_RUN_TRACE) {
+                if (p.slab) hipLaunchKernelGGL(chain_items_trace_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
+                else hipLaunchKernelGGL(chain_items_trace_kernel, dim3(blocks), dim3(64), ci_trace_lds_bytes(p.lds_np), stream, p);
+            } else return VGK_EINVAL;
+        }
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
     int run_minimizer_choose(const MzChooseParams& p, uint32_t blocks) override {

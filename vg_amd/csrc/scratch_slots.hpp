@@ -43,6 +43,10 @@ enum Slot : int {
     // ---- gssw_wide_api.cpp, chain_api.cpp (nothing stays)
     WIDE_PROBS, WIDE_ORDER, WIDE_COLINFO, WIDE_PROF, WIDE_NODES, WIDE_PREDS, WIDE_SCRATCH, WIDE_CARRY, WIDE_TB, WIDE_BEST, WIDE_RESULTS, WIDE_OPS,
     CHAIN_UP, CHAIN_TAB, CHAIN_RES, CHAIN_WORK_M, CHAIN_WORK_E, CHAIN_OUT_M, CHAIN_OUT_E,
+    // ---- chain_items_api.cpp (nothing stays): the problems and their inputs, the jump tables, the launch's problem numbers; per candidate the
+    // indel; per anchor the group counts, their prefix sums and the scatter's cursors; the groups; the error flag; the table and the outputs; the slabs
+    CITEMS_PROBS, CITEMS_CAND_OFF, CITEMS_ANCHORS, CITEMS_CANDS, CITEMS_JUMP, CITEMS_IDS, CITEMS_INDEL, CITEMS_COUNT, CITEMS_FIRST, CITEMS_CURSOR, CITEMS_GROUPED,
+    CITEMS_FLAGS, CITEMS_TSCORE, CITEMS_TSOURCE, CITEMS_CHAINS, CITEMS_NCHAINS, CITEMS_ITEMS, CITEMS_REC_RIGHT, CITEMS_REC_LEFT, CITEMS_SLAB,
     SLOT_COUNT,                        // sizes vgk_ctx::scratch; only aliases follow
 
     // ---- deliberate sharing: a second name for a buffer above, so that a context which uses both paths keeps one set of buffers in HBM.

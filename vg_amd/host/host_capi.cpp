@@ -1104,3 +1104,71 @@ int vgh_batch_add_slot(vgh_batch* b, int slot, vgh_graph* g, const char* read, i
     } catch (std::exception& e) { g_last_error = e.what(); return -1; }
 }
 }
+
+#include "chain_items.hpp"
+#include "vgk_engine.h"
+extern "C" {
+// find_best_chains (chain_items.hpp) for a batch of problems, over the flat arrays of the engine's vgk_chain_items (include/vgk_engine.h) and with its
+// output layout: problem p's chains at chains[chain_off[p] .. chain_off[p + 1]), a chain's anchors and both recombination lists in the problem's own
+// stretch of items / rec_right / rec_left.  verdict (nullable, one byte per candidate): 0 = legal, otherwise add_transition_if_legal's drop (1 .. 5).
+// Problems on `threads` host threads (0 = all).
+int vgh_find_best_chains(const vgk_chain_scheme* scheme, uint32_t n_problems, const uint64_t* anchor_off, const vgk_chain_anchor* anchors,
+                         const uint64_t* cand_off, const vgk_chain_candidate* candidates, const uint32_t* read_lookback, const uint32_t* indel_limit,
+                         uint64_t* chain_off, vgk_chain_found* chains, uint32_t* items, uint32_t* rec_right, uint32_t* rec_left,
+                         int32_t* table_score, uint32_t* table_source, uint8_t* verdict, int threads) {
+    try {
+        ChainScoringScheme S; S.item_bonus = scheme->item_bonus; S.gap_scale = scheme->gap_scale; S.recombination_penalty = scheme->recombination_penalty; S.consistency_bonus = scheme->consistency_bonus;
+        std::vector<ChainsResult> results(n_problems);
+        unsigned T = threads > 0 ? (unsigned)threads : std::max(1u, std::thread::hardware_concurrency());
+        T = std::min<unsigned>(T, std::max<uint32_t>(1, n_problems));
+        std::atomic<uint32_t> next{0}; std::atomic<bool> failed{false}; std::string what; std::mutex what_mu;
+        auto work = [&]() {
+            try {
+                std::vector<vgamd::Anchor> to_chain; std::vector<candidate_transition> cands; std::vector<TracedScore> table; std::vector<transition_info> probe;
+                for (uint32_t p = next.fetch_add(1); p < n_problems; p = next.fetch_add(1)) {
+                    const uint64_t a0 = anchor_off[p], a1 = anchor_off[p + 1], c0 = cand_off[p], c1 = cand_off[p + 1];
+                    to_chain.assign((size_t)(a1 - a0), vgamd::Anchor());
+                    for (uint64_t i = a0; i < a1; ++i) {
+                        vgamd::Anchor& x = to_chain[(size_t)(i - a0)]; const vgk_chain_anchor& y = anchors[i];
+                        x.start = y.read_start; x.size = y.length; x.margin_before = y.margin_before; x.margin_after = y.margin_after; x.points = y.score;
+                        x.start_offset = y.start_hint_offset; x.end_offset = y.end_hint_offset; x.seed_length = y.base_seed_length; x.start_paths = y.start_paths; x.end_paths = y.end_paths;
+                    }
+                    cands.clear();
+                    for (uint64_t c = c0; c < c1; ++c) cands.push_back({candidates[c].from, candidates[c].to, candidates[c].graph_distance});
+                    const size_t lookback = read_lookback ? read_lookback[p] : scheme->max_read_lookback_bases, limit = indel_limit ? indel_limit[p] : scheme->max_indel_bases;
+                    const size_t no_limit = std::numeric_limits<size_t>::max();
+                    if (verdict) for (uint64_t c = c0; c < c1; ++c) {
+                        probe.clear();
+                        verdict[c] = (uint8_t)add_transition_if_legal(probe, to_chain, lookback == 0xffffffffu ? no_limit : lookback, limit, candidates[c].from, candidates[c].to, candidates[c].graph_distance);
+                    }
+                    results[p] = find_best_chains(to_chain, cands, S, scheme->max_chains, lookback == 0xffffffffu ? no_limit : lookback, limit, &table);
+                    for (uint64_t i = a0; i < a1; ++i) {
+                        if (table_score) table_score[i] = table[(size_t)(i - a0)].score;
+                        if (table_source) table_source[i] = table[(size_t)(i - a0)].source == TracedScore::nowhere() ? 0xffffffffu : (uint32_t)table[(size_t)(i - a0)].source;
+                    }
+                }
+            } catch (std::exception& e) { failed = true; std::lock_guard<std::mutex> lk(what_mu); what = e.what(); }
+        };
+        std::vector<std::thread> pool;
+        for (unsigned t = 1; t < T; ++t) pool.emplace_back(work);
+        work();
+        for (std::thread& t : pool) t.join();
+        if (failed) { g_last_error = what; return -1; }
+        uint64_t slot = 0;
+        for (uint32_t p = 0; p < n_problems; ++p) {
+            chain_off[p] = slot;
+            uint32_t at = (uint32_t)anchor_off[p];
+            for (const ChainWithRec& c : results[p].chains) {
+                const std::vector<size_t>& ix = c.scored_chain.second;
+                chains[slot++] = vgk_chain_found{c.scored_chain.first, at, (uint32_t)ix.size(), at, (uint32_t)c.rec_positions.size(), (uint32_t)c.left_rec_positions.size()};
+                for (size_t i = 0; i < ix.size(); ++i) items[at + i] = (uint32_t)ix[i];
+                for (size_t i = 0; i < c.rec_positions.size(); ++i) rec_right[at + i] = (uint32_t)c.rec_positions[i];
+                for (size_t i = 0; i < c.left_rec_positions.size(); ++i) rec_left[at + i] = (uint32_t)c.left_rec_positions[i];
+                at += (uint32_t)ix.size();
+            }
+        }
+        chain_off[n_problems] = slot;
+        return 0;
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+}  // extern "C"

@@ -448,6 +448,46 @@ def seed_long_reads(eng, mindex, reads, read_off, k, policy=None, threads=0, cho
 
 
 # ---- configs[4] with the whole stage in the host shim (vg_amd/host/chain_stage.cpp) -----------------------------------------------------
+def pack_chain_problems(problems):
+    """problems: per (read, tree) a pair (anchors CHAIN_ANCHOR_DT, candidates CHAIN_CANDIDATE_DT) -> (anchor_off, anchors, cand_off, candidates) as vgk_chain_items takes them"""
+    aoff = np.concatenate([[0], np.cumsum([len(a) for a, _ in problems])]).astype(np.uint64)
+    coff = np.concatenate([[0], np.cumsum([len(c) for _, c in problems])]).astype(np.uint64)
+    anchors = np.concatenate([np.asarray(a, dtype=capi.CHAIN_ANCHOR_DT) for a, _ in problems]) if problems else np.zeros(0, dtype=capi.CHAIN_ANCHOR_DT)
+    cands = np.concatenate([np.asarray(c, dtype=capi.CHAIN_CANDIDATE_DT) for _, c in problems]) if problems else np.zeros(0, dtype=capi.CHAIN_CANDIDATE_DT)
+    return aoff, anchors, coff, cands
+
+
+def unpack_chains(out, anchor_off):
+    """vgk_chain_items' flat answer -> per problem dict(chains=[dict(score, items, rec_positions, left_rec_positions, rec_intervals)], table=[(score, source or None)])"""
+    res = []
+    for p in range(len(anchor_off) - 1):
+        chains = []
+        for c in out["chains"][int(out["chain_off"][p]):int(out["chain_off"][p + 1])]:
+            ib, rb = int(c["item_begin"]), int(c["rec_begin"])
+            right = out["rec_right"][rb:rb + int(c["n_rec"])].tolist(); left = out["rec_left"][rb:rb + int(c["n_rec_left"])].tolist()
+            chains.append(dict(score=int(c["score"]), items=out["items"][ib:ib + int(c["n_items"])].tolist(), rec_positions=right, left_rec_positions=left,
+                               rec_intervals=list(zip(left, right)) if len(left) == len(right) else []))
+        a, b = int(anchor_off[p]), int(anchor_off[p + 1])
+        table = [(int(s), None if int(f) == capi.CHAIN_NOWHERE else int(f)) for s, f in zip(out["table_score"][a:b], out["table_source"][a:b])]
+        res.append(dict(chains=chains, table=table))
+    return res
+
+
+def find_best_chains(eng, problems, scheme=None, read_lookback=None, indel_limit=None):
+    """algorithms::find_best_chains (src/algorithms/chain_items.cpp:735-877) for a batch of (read, tree) problems on the device, one call
+    (vgk_chain_items, include/vgk_engine.h).  problems: pairs (anchors, candidate transitions) — the anchors in sort_anchor_indexes' order, the candidates
+    (from, to, graph distance) as the zip-code tree reports them, in any order.  eng = None: the host shim's find_best_chains (the checker) instead.
+    -> per problem dict(chains best first, table); see unpack_chains"""
+    aoff, anchors, coff, cands = pack_chain_problems(problems)
+    if eng is not None:
+        out = eng.chain_items(scheme, aoff, anchors, coff, cands, read_lookback, indel_limit)
+    else:
+        rc, out = capi.chain_items_call(_host_lib().vgh_find_best_chains, (), scheme, aoff, anchors, coff, cands, read_lookback, indel_limit, tail=(ctypes.c_void_p(None), ctypes.c_int(0)))
+        if rc:
+            raise RuntimeError(_host_lib().vgh_last_error().decode())
+    return unpack_chains(out, aoff)
+
+
 class ChainStage:
     """MinimizerMapper's chain alignment for a batch of reads, in C++ behind one call (vgh_chain_stage): every link through WFAExtender;
     what it declines through align_sequence_between_consistently — the local graph between / beyond the anchors cut out of the haplotype

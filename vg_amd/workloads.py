@@ -1076,3 +1076,42 @@ class PairedWorkload:
         w.truth = dict(self.truth, hap=self.truth["hap"][:k], start=self.truth["start"][:k], frag=self.truth["frag"][:k], flip=self.truth["flip"][:k],
                        hard=self.truth["hard"][self.truth["hard"] < k])
         return w
+
+
+class ChainItemsWorkload:
+    """Chaining problems for vgk_chain_items (include/vgk_engine.h), one per (read, zip-code tree): anchors planted collinearly along a read of
+    `read_len` bases — their graph coordinates drift by small indels —, decoy anchors anywhere in the read at graph coordinates far from the planted
+    line, and as candidate transitions every ordered pair of anchors whose start points lie within `graph_lookback` bases of each other on a linear
+    graph coordinate (what a zip-code tree reports before add_transition_if_legal: pairs that run backwards in the read are among them).  The hint
+    point of an anchor is its start: start_hint_offset 0, end_hint_offset = length.  problems[p] = (anchors, candidates) in sort_anchor_indexes'
+    order; truth[p] = the planted anchors' numbers in that order, left to right."""
+
+    def __init__(self, n_problems, seed=0, read_len=3000, n_planted=25, n_decoys=75, graph_lookback=3000, seed_length=29, max_drift=3, min_len=20, max_len=60):
+        rng = np.random.default_rng(seed)
+        self.n = n_problems; self.read_len = read_len; self.graph_lookback = graph_lookback
+        self.problems = []; self.truth = []
+        slot = read_len // max(n_planted, 1)
+        assert n_planted == 0 or slot > max_len + 2, "the planted anchors do not fit the read"
+        for _ in range(n_problems):
+            m = n_planted + n_decoys
+            length = rng.integers(min_len, max_len + 1, m).astype(np.int64)
+            read_start = np.empty(m, dtype=np.int64); graph_start = np.empty(m, dtype=np.int64)
+            # planted: one per stretch of the read, so none overlaps another; the graph coordinate follows the read with a drift that changes by small steps
+            read_start[:n_planted] = np.arange(n_planted) * slot + rng.integers(0, slot - max_len - 1, n_planted) + 1
+            drift = np.cumsum(np.where(rng.random(n_planted) < 0.3, rng.integers(-max_drift, max_drift + 1, n_planted), 0))
+            origin = int(rng.integers(1000, 5000))
+            graph_start[:n_planted] = origin + read_start[:n_planted] + drift
+            # decoys: anywhere in the read, far off the planted line in the graph
+            read_start[n_planted:] = rng.integers(1, read_len - max_len, n_decoys)
+            graph_start[n_planted:] = rng.integers(20 * read_len, 60 * read_len, n_decoys)
+            order = np.lexsort((-(read_start + length), read_start))
+            anchors = np.zeros(m, dtype=capi.CHAIN_ANCHOR_DT)
+            anchors["read_start"] = read_start[order]; anchors["length"] = length[order]; anchors["score"] = length[order]
+            anchors["end_hint_offset"] = length[order]; anchors["base_seed_length"] = seed_length; anchors["start_paths"] = 1; anchors["end_paths"] = 1
+            g = graph_start[order]
+            d = g[None, :] - g[:, None]
+            frm, to = np.nonzero((d >= 0) & (d <= graph_lookback) & ~np.eye(m, dtype=bool))
+            cands = np.zeros(len(frm), dtype=capi.CHAIN_CANDIDATE_DT)
+            cands["from"] = frm; cands["to"] = to; cands["graph_distance"] = d[frm, to]
+            where = np.empty(m, dtype=np.int64); where[order] = np.arange(m)
+            self.problems.append((anchors, cands)); self.truth.append(where[:n_planted].tolist())
