@@ -21,7 +21,9 @@
  *   each pinning node's last column.  To keep renderings distinct, a gap is never opened directly after a gap of the same
  *   kind was opened (the two would print as one longer gap), sources worth 0 or less are not entered, diagonal sources through
  *   predecessor cells worth 0 count as one (the alignment starts at the current cell either way), and a walk ends only where
- *   the DP value reaches 0 or the read is used up.
+ *   the DP value reaches 0 or the read is used up.  With gap_open == gap_extend the default walk may take "open from H" in a gap
+ *   state where only the gap explains that H, and re-open the gap there; the "extend" source of the same cell would print as that very
+ *   walk and is not proposed.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -150,6 +152,8 @@ static void walk(const Ctx* x, const Alt* alt, const int* start_cols, Queue* q, 
             for (uint32_t k = 0; k < ns; ++k) {
                 if (k == take || src[k].value <= 0) continue;
                 if (st != ST_H && src[k].st == ST_H && !viable(x, src[k].r, src[k].c, st == ST_E, st == ST_F)) continue;   /* would print as the gap-extend walk */
+                if (st != ST_H && src[k].st == st && src[take].st == ST_H && src[take].r == src[k].r && src[take].c == src[k].c &&
+                    !viable(x, src[take].r, src[take].c, st == ST_E, st == ST_F)) continue;   /* gap_open == gap_extend: the walk taken re-opens this gap there and prints as this one */
                 const int32_t sc2 = start_value - lost - (value - src[k].value);
                 if (sc2 <= 0) continue;
                 Alt a; a.score = sc2; a.start = alt->start; a.n = alt->n + 1; a.d = (Defl*)malloc(sizeof(Defl) * a.n);

@@ -49,6 +49,57 @@ empty nodes.  Narrow bands: at most this optimum.
 (d) check_alignment: see its docstring.
 
 (e) WFA connect: wfa_connect_optimum, see its docstring.
+
+(f) The k best banded global alignments (align_global_banded_multi) with a band that excludes nothing:
+banded_kbest_scores, the k highest scores over DISTINCT alignments of (c), in descending order, fewer only when fewer
+alignments exist.
+  * an alignment is a source-to-sink walk (empty nodes are part of the walk: two walks that differ only in their empty
+    nodes are two walks) and a sequence of single-base ops M / I / D that consumes the whole read and every base of
+    the walk.  Two alignments are the same only if walk and ops are the same.  Scores are those of (c): an I may
+    follow a D and a D an I, each paying its own gap_open, so an alignment has exactly one path through the states
+    "last op was M / I / D" and the k-best dynamic program over those three states counts nothing twice;
+  * EXCLUSION 1 (whole-read lead insertion): an alignment that begins with the insertion of the WHOLE read while its
+    walk holds graph bases (which are then all deleted: 2I2D, 3I1D, 1I6D) is not an alignment of this family.  The
+    reference's matrix has no row above read base 0: in the first column of a node that can begin a walk the
+    insertion-then-deletion entry of row r stands for r + 1 inserted bases, and the entry of the bottom row is set to
+    "none" (src/banded_global_aligner.cpp:577-579, :597-598, :604-605; restated in oracle/vgo_banded.c fill_node,
+    "implied lead gaps of a source column").  The whole read inserted on a walk of empty nodes alone IS an alignment,
+    one per such walk (next_empty_alignment, :2616-2668; the walks are listed at :2426-2563);
+  * EXCLUSION 2 (empty nodes in front of a walk count once): alignments whose walks differ only in the chain of empty
+    nodes in front of their first non-empty node are one alignment.  The traceback ends in the first column of that
+    node and writes ONE chain of empty nodes in front of it, the last its search met, whichever empty source the
+    chain begins at (empty_source_path: :1288-1295, :1393-1398, written out at :1739-1743);
+  * EXCLUSION 3 (no deletion under a first column's bottom row): let n be a node that can begin a walk (a source, or a
+    node reached from an empty source over empty nodes alone).  An alignment that deletes n's first base with the
+    whole read already consumed is not an alignment of this family, EVEN when its walk enters n from a predecessor
+    with bases: the "none" of exclusion 1 is written into the cell after every predecessor has been merged into it
+    (:604-605, behind the loop over the seeds :373-544), so it removes what they had put there.  On a one-base read
+    this is every deletion of such a first base behind read base 0;
+  * what stays outside the definition, counted by the tests and held to the superset bound only: where a node n can
+    begin a walk AND has predecessors with bases, the traceback takes "the walk begins here" only when no predecessor
+    explains the cell, and never proposes it as an alternate (:1661-1736: the proposals at :1696-1701 and :1717-1722
+    run over traceback_source_nodes, which the search over the seeds at :1386-1399 never adds an empty source to), so
+    alignments that begin at n's empty source are missing from the alternates whenever a predecessor explains the
+    cell.  That depends on the scores in the cell, not on (walk, ops) alone: no exclusion is stated for it;
+  * DUPLICATES: a deflection across an edge names the predecessor with bases it lands on, not the empty nodes on the
+    way (:1313-1314, :2724), and when taken follows the first chain of empty nodes that reaches that predecessor
+    (:1176-1210, "don't have a better way of looking this up right now").  Where a node reaches one predecessor over
+    two chains of empty nodes (the edge itself being the chain of none) the alternate over the second chain comes
+    out as a copy of the one over the first: the same score, so the score list is that of the definition, but (walk,
+    ops) twice.  ambiguous_empty_chains says whether a problem has such an edge.
+  exclude_whole_read_lead_insertion = False drops all three exclusions: a superset of the family;
+  * narrow bands and what the enumeration of the reference leaves out among walks through empty nodes (DESIGN.md,
+    "k-best against the definition"): at every rank at most the score of that superset.
+
+(g) The k best right-pinned alignments (align_pinned_multi): gssw's multi-traceback returns maximal tracebacks from
+the best end cell, a procedure and not a problem statement, so there is no exact definition here, only a bound:
+pinned_kbest_bound, the k highest POSITIVE scores over every distinct pinned alignment of (a):
+  * the start is free: before any graph base c, with any number i < L of read bases soft-clipped, and the first op may
+    be M, I or D; alignments are distinct when (c, i, ops) differ;
+  * the bonus sits on read base 0 as in (a), earned by a diagonal move only;
+  * the end: read base L-1 consumed, in the last column of a pinning node, in any of the states M, I, D.
+Every alignment a pinned multi-traceback can return is one of these, so its j-th score is at most the j-th of the
+bound; the first of the bound is the PINNED optimum of (a).
 """
 import numpy as np
 
@@ -201,6 +252,138 @@ def banded_global_optimum(problem, scoring, qual_adj=None):
         for p in pr:
             has_succ[p] = True
     return max(int(outH[v][sc.L]) for v in range(len(outH)) if not has_succ[v])
+
+
+def _top(lists, k):
+    """rows of score lists side by side -> per row the k highest in descending order (a multiset union: nothing is merged away)"""
+    a = np.concatenate(lists, axis=1)
+    a = -np.sort(-a, axis=1)[:, :k]
+    if a.shape[1] < k:
+        a = np.concatenate([a, np.full((a.shape[0], k - a.shape[1]), NEG, dtype=np.int64)], axis=1)
+    a[a < NEG // 2] = NEG
+    return a
+
+
+def _kbest_column(sub_g, Mp, Ip, Dp, go, ge, k):
+    """One graph base.  Row i = i read bases consumed; (Mp, Ip, Dp) the k best scores of distinct partial alignments in front of the base whose
+    last op was M / I / D -> the same behind it.  sub_g[i] = the base against read base i."""
+    L = len(sub_g)
+    M = np.full((L + 1, k), NEG, dtype=np.int64)
+    M[1:] = _top([Mp, Ip, Dp], k)[:-1] + sub_g[:, None]
+    M[M < NEG // 2] = NEG
+    D = _top([Mp - go, Ip - go, Dp - ge], k)
+    I = np.full((L + 1, k), NEG, dtype=np.int64)
+    for i in range(1, L + 1):
+        I[i] = _top([M[i - 1:i] - go, D[i - 1:i] - go, I[i - 1:i] - ge], k)[0]
+    return M, I, D
+
+
+def _descending(lists, k):
+    a = np.concatenate([np.ravel(x) for x in lists]) if lists else np.zeros(0, dtype=np.int64)
+    return [int(x) for x in -np.sort(-a[a > NEG // 2])[:k]]
+
+
+def banded_kbest_scores(problem, scoring, k, qual_adj=None, exclude_whole_read_lead_insertion=True):
+    """(f): the k highest scores of distinct global alignments, descending; shorter than k only when fewer exist.
+    exclude_whole_read_lead_insertion = False: without any of (f)'s exclusions, the superset."""
+    exclude = exclude_whole_read_lead_insertion
+    sc = Scores(problem, scoring, MODE_BANDED, qual_adj)
+    L, go, ge = sc.L, sc.go, sc.ge
+    nodes, preds = problem["nodes"], problem["preds"]
+    none = np.full((L + 1, k), NEG, dtype=np.int64)
+    M0 = none.copy(); M0[0, 0] = 0
+    I0 = none.copy(); I0[1:, 0] = -(go + np.arange(L, dtype=np.int64) * ge)             # the insertion ramp in front of a walk's first base
+    whole = int(I0[L, 0])
+    if exclude:
+        I0[L, 0] = NEG                           # EXCLUSION 1: the whole read inserted survives only on walks of empty nodes alone, counted by `chains`
+    # per node: the lists behind it of what has consumed a graph base, and the number of chains of empty nodes alone that end here
+    out = []
+    for v, s in enumerate(nodes):
+        if preds[v]:
+            M, I, D = (_top([out[p][x] for p in preds[v]], k) for x in range(3))
+            chains = sum(out[p][3] for p in preds[v])
+        else:
+            M, I, D, chains = none, none, none, 1
+        for g in _codes(s):
+            if chains:                           # a walk may begin here.  EXCLUSION 2: over whichever chain of empty nodes, once
+                n = 1 if exclude else min(chains, k)
+                M, I = _top([M] + [M0] * n, k), _top([I] + [I0] * n, k)
+            M, I, D = _kbest_column(sc.sub[g], M, I, D, go, ge, k)
+            if chains and exclude:
+                D[L] = NEG                       # EXCLUSIONS 1 and 3
+            chains = 0
+        out.append((M, I, D, chains))
+    has_succ = [False] * len(nodes)
+    for pr in preds:
+        for p in pr:
+            has_succ[p] = True
+    ends = []
+    for v in range(len(nodes)):
+        if not has_succ[v]:
+            M, I, D, chains = out[v]
+            ends += [M[L], I[L], D[L], np.full(min(chains, k), whole, dtype=np.int64)]     # a walk of empty nodes alone: the whole read inserted, once per walk
+    return _descending(ends, k)
+
+
+def ambiguous_empty_chains(problem):
+    """(f) DUPLICATES: does some node reach one predecessor with bases over two chains of empty nodes?"""
+    nodes, preds = problem["nodes"], problem["preds"]
+    for v in range(len(nodes)):
+        seen, stack = set(), list(preds[v])
+        while stack:
+            p = stack.pop()
+            if nodes[p]:
+                if p in seen:
+                    return True
+                seen.add(p)
+            else:
+                stack += preds[p]
+    return False
+
+
+def empty_chain_walks(problem, walk):
+    """(f) DUPLICATES: the number of walks that differ from `walk` (a list of nodes) only in the empty nodes BETWEEN two of its nodes with bases:
+    the product, over consecutive nodes with bases, of the number of chains of empty nodes that join them.  The copies of one (walk, ops) among a
+    problem's alternates stand for such walks, so there are at most this many."""
+    nodes, preds = problem["nodes"], problem["preds"]
+    based = [v for v in walk if nodes[v]]
+    total = 1
+    for u, v in zip(based, based[1:]):
+        n, stack = 0, list(preds[v])
+        while stack:
+            p = stack.pop()
+            if p == u:
+                n += 1
+            elif not nodes[p]:
+                stack += preds[p]
+        total *= max(n, 1)
+    return total
+
+
+def pinned_kbest_bound(problem, scoring, k, qual_adj=None):
+    """(g): the k highest positive scores over every pinned alignment, descending: an upper bound, rank by rank, on what a pinned multi-traceback returns."""
+    sc = Scores(problem, scoring, MODE_PINNED, qual_adj)
+    L, go, ge = sc.L, sc.go, sc.ge
+    nodes, preds = problem["nodes"], problem["preds"]
+    none = np.full((L + 1, k), NEG, dtype=np.int64)
+    fresh = np.zeros((L + 1, 1), dtype=np.int64); fresh[L] = NEG               # a start in front of a base with i < L read bases soft-clipped
+    lead = np.full((L + 1, L), NEG, dtype=np.int64)                            # ... and the insertions that begin at such a start: j - i bases, for every i < j
+    for j in range(1, L + 1):
+        lead[j, :j] = -(go + np.arange(j, dtype=np.int64) * ge)
+    lead = _top([lead], k)
+    out, ends = [], []
+    for v, s in enumerate(nodes):
+        assert len(s) > 0
+        if preds[v]:
+            M, I, D = (_top([out[p][x] for p in preds[v]], k) for x in range(3))
+        else:
+            M, I, D = none, none, none
+        for g in _codes(s):
+            M, I, D = _kbest_column(sc.sub[g], _top([M, fresh], k), _top([I, lead], k), D, go, ge, k)
+        out.append((M, I, D))
+        if problem["pinning"][v]:
+            ends += [M[L], I[L], D[L]]
+    return [x for x in _descending(ends, k) if x > 0]
 
 
 def optimum(problem, scoring, mode, qual_adj=None):

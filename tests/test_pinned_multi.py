@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import refdp
 import util
 from gen import problem_set, random_problem
 from vg_amd import capi
@@ -131,6 +132,7 @@ def compare_engines(lib, seeds, n_problems=40, max_alt=30, on_device=True):
                 a, b = ra[i, k], rb[i, k]
                 assert a["score"] == b["score"] and a["status"] == b["status"] == 0 and a["first_offset"] == b["first_offset"], (s, i, k, a, b)
                 assert capi.cigar_string(a, oa) == capi.cigar_string(b, ob), (s, i, k)
+                refdp.check_alignment(problems[i], eng.scoring, refdp.MODE_PINNED, b, ob[int(b["ops_begin"]):int(b["ops_begin"]) + int(b["n_ops"])])      # a pinned alignment that re-scores to b["score"]
             if ca[i]:
                 assert list(ra[i, :ca[i]]["score"]) == sorted(ra[i, :ca[i]]["score"], reverse=True)
                 rendered = [(int(ra[i, k]["first_offset"]), capi.cigar_string(ra[i, k], oa)) for k in range(int(ca[i]))]

@@ -161,6 +161,8 @@ private:
                 for (size_t k = 0; k < src.size(); ++k) {
                     if (k == take || src[k].value <= 0) continue;
                     if (st != AT_H && src[k].st == AT_H && !explains(src[k].r, src[k].c, st == AT_E, st == AT_F)) continue;
+                    if (st != AT_H && src[k].st == st && src[take].st == AT_H && src[take].r == src[k].r && src[take].c == src[k].c &&
+                        !explains(src[take].r, src[take].c, st == AT_E, st == AT_F)) continue;      // gap_open == gap_extend: the walk taken re-opens this gap there and prints as this one
                     const int32_t score2 = start_value - lost - (value - src[k].value);
                     if (score2 <= 0) continue;
                     Alternate a{score2, alt.start, alt.deflections};

@@ -187,6 +187,8 @@ VGK_HD void gssw_multi_one(const GsswMultiParams& P, uint32_t i) {
                 for (uint32_t k = 0; k < n_src; ++k) {
                     if (k == take || src[k].value <= 0) continue;
                     if (st != MT_H && src[k].st == MT_H && !w.explains(src[k].r, src[k].c, src[k].v, st == MT_E, st == MT_F)) continue;
+                    if (st != MT_H && src[k].st == st && src[take].st == MT_H && src[take].r == src[k].r && src[take].c == src[k].c &&
+                        !w.explains(src[take].r, src[take].c, src[take].v, st == MT_E, st == MT_F)) continue;      // gap_open == gap_extend: the walk taken re-opens this gap there and prints as this one
                     const int32_t score2 = start_value - lost - (value - src[k].value);
                     if (score2 <= 0) continue;
                     w.offer(score2, alt.start, &alt, alt.n_defl, true, MtDefl{r, c, (uint32_t)st | (k << 8)}, room);
