@@ -69,3 +69,10 @@ chainitems: tests/emu/libvgamd_chainitems.so
 tests/emu/libvgamd_chainitems.so: tests/emu/chain_items_driver.cpp $(LIB_HDRS)
 	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -shared -o $@ $<
 .PHONY: chainitems
+
+# test-only: the serial form of the device rule that packs windows of a resident graph for the wide kernels (gssw_wide_pack_device.hpp) beside the
+# host packer of explicit graphs (gssw_wide_pack.hpp) behind one C call
+widewin: tests/emu/libvgamd_widewin.so
+tests/emu/libvgamd_widewin.so: tests/emu/wide_windows_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -shared -o $@ $<
+.PHONY: widewin

@@ -127,6 +127,28 @@ int vgk_chain_items_limits(uint32_t out[4]);
 /* Device time (ms) of the last vgk_chain_items call on this context: legality + grouping | DP | traceback */
 int vgk_chain_items_last_ms(vgk_ctx* ctx, double ms[3]);
 
+/* ---- windows of the resident graph, of any read length: the wide route on the device ------------------------------------------------------
+ * vgk_gssw_pack_windows (vgk.h) takes what the packed kernels take: at most 1024 DP rows, scores inside 11 bits; a longer window fails the whole
+ * pack with VGK_ETOOLONG.  This one-call entry takes windows of any read length and scoring and answers every problem in its own status, as
+ * vgk_gssw_align does for explicit graphs.  Results are those of vgk_gssw_align on the induced subgraphs of nodes [first_node, first_node + n_nodes):
+ * edges entering from outside are dropped, op.node and end_node count from the window's first node.  Modes: VGK_GSSW_LOCAL and VGK_XDROP_PINNED,
+ * each with or without VGK_GSSW_TRACEBACK.  A quality-adjusted context: VGK_EUNSUPPORTED for the call.
+ *
+ * Windows the packed kernels take run as ONE batch through the window packer, in their original relative order; the others are packed on the
+ * device for the wide kernels (four wavefronts per problem, int32 cells) in sub-batches of at most a quarter of the device's memory
+ * (VGAMD_MAX_BATCH_BYTES, read per call, overrides).  Any graph vgk_gssw_pack_windows accepts is accepted (tail forests included).
+ *
+ * Per problem (zeroed result fields, the rest of the call goes ahead): VGK_EINVAL an empty read or window, a window beyond the graph, a read
+ * beyond reads_bytes, any other mode; VGK_ETOOLONG read_len >= 65535; VGK_ETOOBIG 2^20 graph columns or more; VGK_EOVERFLOW from the kernels;
+ * VGK_EOPS the window's ops do not fit what is left of ops_cap (the score and end cell are still reported).  The ops lie in problem order in
+ * `ops`; *ops_written is their number. */
+int vgk_gssw_align_windows(vgk_ctx* ctx, const vgk_dgraph* graph, const char* reads, size_t reads_bytes,
+                           const vgk_window_problem* problems, uint32_t n,
+                           vgk_result* results /* [n] */, vgk_op* ops, size_t ops_cap, size_t* ops_written);
+/* The last vgk_gssw_align_windows call on this context: 0 device ms of the wide packing kernels, 1 wide fill ms, 2 wide walk ms, 3 windows that
+ * went wide, 4 wide sub-batches, 5 op bytes copied back for the wide windows */
+double vgk_gssw_align_windows_last(vgk_ctx* ctx, int which);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,12 @@ class VgkError(RuntimeError):
     pass
 
 
+# vgk_gssw_align_windows / vgk_gssw_align_windows_last (include/vgk_engine.h)
+ALIGN_WINDOWS_ARGTYPES = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
+                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+ALIGN_WINDOWS_LAST_ARGTYPES = [ctypes.c_void_p, ctypes.c_int]
+
+
 def load_library(path=None):
     path = path or os.environ.get("VGAMD_ENGINE_LIB") or DEFAULT_LIB
     if not os.path.exists(path):
@@ -188,6 +194,10 @@ def load_library(path=None):
     if hasattr(lib, "vgk_gssw_wide_last"):                     # (the oracle has no wide route)
         lib.vgk_gssw_wide_last.restype = ctypes.c_double
         lib.vgk_gssw_wide_last.argtypes = [vp, ctypes.c_int]
+    if hasattr(lib, "vgk_gssw_align_windows"):                 # (engine only: include/vgk_engine.h)
+        lib.vgk_gssw_align_windows.argtypes = ALIGN_WINDOWS_ARGTYPES
+        lib.vgk_gssw_align_windows_last.restype = ctypes.c_double
+        lib.vgk_gssw_align_windows_last.argtypes = ALIGN_WINDOWS_LAST_ARGTYPES
     lib.vgk_xdrop_band_align.argtypes = [vp, vp, u32, vp, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64 * 2)]
     lib.vgk_graph_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
     lib.vgk_graph_destroy.argtypes = [vp]
@@ -459,6 +469,24 @@ class Engine:
         written = ctypes.c_size_t()
         self._check(self.lib.vgk_gssw_align(self.h, ps.ptr, ps.n, res.ctypes.data, ops.ctypes.data, cap, ctypes.byref(written)), "vgk_gssw_align")
         return res, ops[:written.value]
+
+    def align_windows_call(self, graph, ws, ops_cap=None):
+        """vgk_gssw_align_windows (the one-call form over a ResidentGraph: windows of any read length, each answered in its own status; the wide
+        kernels take what the packed ones do not) -> (results, ops); ops_cap: entries of the op array (default: room for every window's ops)"""
+        res = np.zeros(ws.n, dtype=RESULT_DT)
+        if ops_cap is None:
+            ops_cap = int(np.diff(ws.read_off).sum() + np.diff(ws.seq_off).sum() + 4 * ws.n)
+        ops = np.zeros(max(int(ops_cap), 1), dtype=OP_DT)
+        written = ctypes.c_size_t()
+        reads = ws.reads.ctypes.data_as(ctypes.c_char_p)
+        self._check(self.lib.vgk_gssw_align_windows(self.h, graph.h, reads, ws.reads.size, ws.array.ctypes.data, ws.n, res.ctypes.data,
+                                                    ops.ctypes.data, int(ops_cap), ctypes.byref(written)), "vgk_gssw_align_windows")
+        return res, ops[:written.value]
+
+    def align_windows_last(self, which):
+        """vgk_gssw_align_windows_last: 0 wide packing kernels ms, 1 wide fill ms, 2 wide walk ms, 3 windows that went wide, 4 wide sub-batches,
+        5 op bytes copied back for the wide windows"""
+        return float(self.lib.vgk_gssw_align_windows_last(self.h, which))
 
     def wide_last(self, which):
         """vgk_gssw_wide_last: the wide route's share of the last align_call (0 fill ms, 1 traceback ms, 2 cells, 3 traced cells, 4 launches)"""

@@ -19,6 +19,7 @@
 #include "tail_device.hpp"
 #include "minimizer_device.hpp"
 #include "gssw_wide_device.hpp"
+#include "gssw_wide_pack_device.hpp"
 #include "rescue_requests_device.hpp"
 #include "chain_device.hpp"
 #include "chain_items_device.hpp"
@@ -139,6 +140,9 @@ public:
     // the wide route of vgk_gssw_align (gssw_wide_device.hpp): a workgroup of four wavefronts per problem, p.order[0 .. n8) with 8 rows
     // per lane, p.order[n8 .. n8 + n16) with 16; then the tracebacks, one lane per problem.  Asynchronous on the main stream.
     virtual int   run_gssw_wide(const WideParams& p, uint32_t n8, uint32_t n16) = 0;
+    // one stage of the wide kernels' packing for windows of the resident graph (gssw_wide_pack_device.hpp: WW_RUN_*), asynchronous on the main
+    // stream: a lane per problem of the call (classify), or the stages of one sub-batch of p.m wide windows.  Optional
+    virtual int   run_wide_windows(const WideWinParams& p, int what) { (void)p; (void)what; return VGK_EUNSUPPORTED; }
     // X-drop with dozeu's band (vgk_xdrop_band_align): one wavefront per problem, the matrices stay for the host's traceback;
     // last_ms(7) = kernel ms
     virtual int   run_xdrop_band(const GsswMatrixParams& p) = 0;

@@ -1905,6 +1905,7 @@ public:
         hipEventRecord(wev[2], stream); wide_pending = true;
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
+    int run_wide_windows(const WideWinParams& p, int what) override { hipSetDevice(dev); return hip_wide_windows(p, what, (uint32_t)std::max(1, prop.multiProcessorCount), stream); }
     int run_xdrop_band(const GsswMatrixParams& p) override {
         ms_xband = 0.f;
         if (!p.n) return VGK_OK;

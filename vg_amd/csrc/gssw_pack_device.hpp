@@ -258,6 +258,7 @@ VGK_HD void win_size_one(const WinParams& P, uint32_t i, WinAcc& acc) {
     if (p.read_len == 0 || p.n_nodes == 0 || (unsigned long long)p.first_node + p.n_nodes > P.g.n_nodes ||
         p.read_off + p.read_len > P.raw_bytes || p.read_off + p.read_len < p.read_off) status = VGK_EINVAL;
     else if (mode != VGK_GSSW_LOCAL && mode != VGK_XDROP_PINNED) status = VGK_EINVAL;      // pinned windows: not offered (the pinning nodes depend on where the window ends)
+    // (longer windows, and scorings beyond the 11 bits tested next: vgk_gssw_align_windows sends those to the wide kernels, gssw_wide_pack_device.hpp)
     else if (rows > 1024) status = VGK_ETOOLONG;
     else if ((long long)rows * (P.max_score > 0 ? P.max_score : 0) + 2ll * P.max_bonus > 2046) status = VGK_EUNSUPPORTED;
     else if (xdrop && (long long)p.read_len * (P.max_score > 0 ? P.max_score : 0) + P.max_bonus >= (long long)XOFF) status = VGK_EUNSUPPORTED;

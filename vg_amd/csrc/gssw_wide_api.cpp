@@ -14,17 +14,18 @@
 #include "batch.hpp"
 #include "ctx.hpp"
 #include "gssw_wide.hpp"
+#include "gssw_wide_pack.hpp"
 
 using namespace vgk;
 
 namespace {
 
-struct Packed {
-    std::vector<WideProb> probs;
-    std::vector<uint8_t> colinfo; std::vector<uint32_t> prof; std::vector<NodeRec> nodes; std::vector<uint32_t> preds;
-    uint64_t scratch = 0, tb = 0, carry = 0, ops = 0;
-    void clear() { probs.clear(); colinfo.clear(); prof.clear(); nodes.clear(); preds.clear(); scratch = tb = carry = ops = 0; }
-};
+using Packed = WidePacked;
+
+// what the packer (gssw_wide_pack.hpp) reads of a context
+WideScoring scoring_view(const vgk_ctx* ctx) {
+    return WideScoring{ctx->sc.matrix, ctx->bias, ctx->sc.full_length_bonus, ctx->has_qa ? ctx->qmat.data() : nullptr, ctx->has_qa ? ctx->qbon.data() : nullptr};
+}
 
 }  // namespace
 
@@ -47,74 +48,6 @@ int vgk::wide_problem_status(const vgk_ctx* ctx, const vgk_gssw_problem& p) {
     return VGK_OK;
 }
 
-// Appends problem p to the arenas.  The caller has checked it with wide_problem_status.
-static void pack_one(const vgk_ctx* ctx, const vgk_gssw_problem& p, Packed& A) {
-    const vgk_graph& g = p.graph;
-    const uint32_t mode = p.flags & 15u; const bool xdrop = mode == VGK_XDROP_PINNED;
-    WideProb d{};
-    d.flags = p.flags; d.L = p.read_len + (xdrop ? 1u : 0u); d.n_nodes = g.n_nodes;
-    d.max_gap = xdrop ? ((std::max<uint32_t>(p.max_gap_length, 1u) + 7u) & ~7u) : 0u;
-    // which full-length bonuses this problem grants, and their values (src/aligner.cpp:401-402, 942-952, 1164-1167)
-    const int first_b = ctx->has_qa ? ctx->qbon[p.qual[0]] : ctx->sc.full_length_bonus;
-    const int last_b = ctx->has_qa ? ctx->qbon[p.qual[p.read_len - 1]] : ctx->sc.full_length_bonus;
-    d.bonus_start = xdrop ? 0 : first_b;
-    d.bonus_end = (mode == VGK_GSSW_PINNED) ? 0 : last_b;
-    // rows per lane: 8 while one strip of 256 lanes holds the read, else 16
-    d.K = d.L <= WIDE_LANES * 8u ? 8u : 16u;
-    d.n_strips = (d.L + WIDE_LANES * d.K - 1) / (WIDE_LANES * d.K);
-    d.Lpad = d.n_strips * WIDE_LANES * d.K;
-    // per-row profile words: byte b = score against reference base b + bias, both bonuses folded in; X-drop row 0 consumes nothing
-    d.prof_off = (uint32_t)A.prof.size();
-    if (xdrop) A.prof.push_back(0u);
-    for (uint32_t r = 0; r < p.read_len; ++r) {
-        const int code = nt_read(p.read[r]);
-        uint32_t w = 0;
-        for (int b4 = 0; b4 < 4; ++b4) {
-            const int s = ctx->has_qa ? ctx->qmat[25 * p.qual[r] + 5 * b4 + code] : ctx->sc.matrix[5 * b4 + code];
-            w |= (uint32_t)(s + (int)ctx->bias) << (8 * b4);
-        }
-        const uint32_t row = r + (xdrop ? 1u : 0u);
-        w += 0x01010101u * row_bonus((uint32_t)d.bonus_start, (uint32_t)d.bonus_end, row, d.L);
-        A.prof.push_back(w);
-    }
-    // nodes whose last column is saved (a successor seeds from it / the pinned end) and nodes seeded from scratch
-    std::vector<uint8_t> store(g.n_nodes, 0), slow(g.n_nodes, 0);
-    for (uint32_t v = 0; v < g.n_nodes; ++v) {
-        const uint32_t pb = g.pred_off[v], pe = g.pred_off[v + 1];
-        const bool chain = (pe - pb == 1) && g.pred_idx[pb] + 1 == v;
-        slow[v] = ((v > 0 || xdrop) && !chain) ? 1 : 0;
-        if (slow[v]) for (uint32_t k = pb; k < pe; ++k) store[g.pred_idx[k]] = 1;
-        if (mode == VGK_GSSW_PINNED && p.pinning[v]) store[v] = 1;
-    }
-    d.col_off = (uint32_t)A.colinfo.size(); d.node_off = (uint32_t)A.nodes.size();
-    uint32_t col = 0, slots = 0, seq_pos = 0;
-    for (uint32_t v = 0; v < g.n_nodes; ++v) {
-        NodeRec nr;
-        nr.col_start = col; nr.col_end = col + g.node_len[v];
-        nr.pred_begin = (uint32_t)A.preds.size(); nr.n_pred = g.pred_off[v + 1] - g.pred_off[v];
-        for (uint32_t k = g.pred_off[v]; k < g.pred_off[v + 1]; ++k) A.preds.push_back(g.pred_idx[k]);
-        nr.slot = store[v] ? (int32_t)slots++ : -1;
-        nr.pinning = (mode == VGK_GSSW_PINNED && p.pinning[v]) ? 1u : 0u;
-        A.nodes.push_back(nr);
-        for (uint32_t k = 0; k < g.node_len[v]; ++k, ++seq_pos) {
-            uint8_t ci = (uint8_t)nt_ref(g.seq[seq_pos]);
-            if (k == 0) { ci |= CI_NODE_START; if (slow[v]) ci |= CI_SEED_SLOW; }
-            if (k + 1 == g.node_len[v] && store[v]) ci |= CI_STORE_END;
-            A.colinfo.push_back(ci);
-        }
-        col = nr.col_end;
-    }
-    d.R = col; d.n_slots = slots;
-    d.scratch_off = A.scratch; A.scratch += (uint64_t)slots * d.Lpad;
-    d.carry_off = A.carry; A.carry += d.n_strips > 1 ? d.R : 0;
-    d.strip_dwords = (uint64_t)(d.R + WIDE_LANES - 1) * WIDE_LANES * (d.K / 8);
-    d.tb_off = A.tb;
-    if (p.flags & VGK_GSSW_TRACEBACK) A.tb += d.strip_dwords * d.n_strips;
-    d.ops_off = (uint32_t)A.ops; d.ops_cap = (p.flags & VGK_GSSW_TRACEBACK) ? p.read_len + d.R + 2 : 0;
-    A.ops += d.ops_cap;
-    A.probs.push_back(d);
-}
-
 int vgk::wide_align(vgk_ctx* ctx, const vgk_gssw_problem* problems, const uint32_t* idx, uint32_t m,
                     vgk_result* results, vgk_op* ops, size_t ops_cap, size_t* ops_at) {
     if (!m) return VGK_OK;
@@ -123,12 +56,11 @@ int vgk::wide_align(vgk_ctx* ctx, const vgk_gssw_problem* problems, const uint32
     uint64_t budget = be->memory_bytes() ? be->memory_bytes() / 4 : (2ull << 30);
     if (const char* e = std::getenv("VGAMD_MAX_BATCH_BYTES")) budget = std::strtoull(e, nullptr, 10);
     std::lock_guard<std::mutex> lock(ctx->mu);
-    Packed A;
+    Packed A; const WideScoring view = scoring_view(ctx);
     // an upper bound of what a problem takes in HBM (every node saved; codes for every cell), to cut the call into sub-batches
     auto estimate = [&](const vgk_gssw_problem& p) -> uint64_t {
         uint64_t R = 0; for (uint32_t v = 0; v < p.graph.n_nodes; ++v) R += p.graph.node_len[v];
-        const uint64_t L = p.read_len + 1ull, K = L <= WIDE_LANES * 8u ? 8 : 16, strips = (L + WIDE_LANES * K - 1) / (WIDE_LANES * K), Lpad = strips * WIDE_LANES * K;
-        return sizeof(WPair) * (p.graph.n_nodes * Lpad + R) + 4 * (R + WIDE_LANES) * WIDE_LANES * (K / 8) * strips + 16 * (L + R) + 64ull * p.graph.n_nodes + 1024;
+        return wide_estimate_bytes(p.read_len, p.graph.n_nodes, R);
     };
     uint32_t begin = 0;
     while (begin < m) {
@@ -143,7 +75,7 @@ int vgk::wide_align(vgk_ctx* ctx, const vgk_gssw_problem* problems, const uint32
             if (!owner.empty() && bytes + pb > budget) break;
             bytes += pb; owner.push_back(end);
         }
-        for (uint32_t k : owner) pack_one(ctx, problems[idx[k]], A);
+        for (uint32_t k : owner) wide_pack_one(view, problems[idx[k]], A);
         const uint32_t n = (uint32_t)owner.size();
         if (n) {
             if (A.colinfo.size() >= (1ull << 32) || A.prof.size() >= (1ull << 32) || A.ops >= (1ull << 32)) return VGK_ETOOBIG;

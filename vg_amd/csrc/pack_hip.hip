@@ -111,6 +111,102 @@ int hip_sort_pairs_u32(const uint32_t* kin, uint32_t* kout, const uint32_t* vin,
     if (hipcub::DeviceRadixSort::SortPairs(tmp, bytes, kin, kout, vin, vout, n, 0, bits, st) != hipSuccess) return VGK_ENODEV;
     return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
 }
+// ---- packing for the wide kernels, windows of the resident graph (gssw_wide_pack_device.hpp) ----------------------------------------------
+__global__ __launch_bounds__(256) void wwin_classify_kernel(const WideWinParams P) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < P.n) wwin_classify_one(P, i);
+}
+// a workgroup per window, windows strided over the grid: a lane per node (flags, the store scatter), then a block scan over the nodes in rounds
+// of 256 for slot numbers and predecessor offsets, then the window's sizes
+__global__ __launch_bounds__(256) void wwin_nodes_kernel(const WideWinParams P) {
+    __shared__ uint32_t wave_s[4], wave_p[4], carry_s, carry_p;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    for (uint32_t k = blockIdx.x; k < P.m; k += gridDim.x) {
+        const WwSub s = P.sub[k];
+        const vgk_window_problem p = P.problems[s.prob];
+        const uint32_t nn = p.n_nodes;
+        for (uint32_t j = threadIdx.x; j < nn; j += 256u) wwin_node_one(P, p, s.tmp_off, j);
+        if (threadIdx.x == 0) { carry_s = 0; carry_p = 0; }
+        __syncthreads();                                                   // every store flag of the window is there
+        for (uint32_t base = 0; base < nn; base += 256u) {
+            const uint32_t j = base + threadIdx.x;
+            const uint32_t cs = j < nn ? P.store[s.tmp_off + j] : 0u, cp = j < nn ? (P.node_flags[s.tmp_off + j] & 0x7fffffffu) : 0u;
+            uint32_t is = cs, ip = cp;
+#pragma unroll
+            for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t us = __shfl_up(is, d, 64), up = __shfl_up(ip, d, 64); if (lane >= d) { is += us; ip += up; } }
+            if (lane == 63) { wave_s[w] = is; wave_p[w] = ip; }
+            __syncthreads();
+            uint32_t bs = carry_s, bp = carry_p;
+            for (uint32_t q = 0; q < w; ++q) { bs += wave_s[q]; bp += wave_p[q]; }
+            if (j < nn) { P.slot_at[s.tmp_off + j] = bs + is - cs; P.pred_at[s.tmp_off + j] = bp + ip - cp; }
+            __syncthreads();
+            if (threadIdx.x == 255) { carry_s = bs + is; carry_p = bp + ip; }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) wwin_sizes_one(P, k, carry_s, carry_p);
+        __syncthreads();
+    }
+}
+// one workgroup: the exclusive sums of every size column over the sub-batch's windows, in 64 bits; offs[c][m] = the column's total
+__global__ __launch_bounds__(256) void wwin_offsets_kernel(const WideWinParams P) {
+    __shared__ unsigned long long wave_t[4], carry;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const unsigned long long m1 = (unsigned long long)P.m + 1;
+    for (uint32_t c = 0; c < WW_NCOL; ++c) {
+        if (threadIdx.x == 0) carry = 0;
+        __syncthreads();
+        for (uint32_t base = 0; base < P.m; base += 256u) {
+            const uint32_t k = base + threadIdx.x;
+            const unsigned long long v = k < P.m ? P.sizes[c * m1 + k] : 0ull;
+            unsigned long long incl = v;
+#pragma unroll
+            for (uint32_t d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(incl, d, 64); if (lane >= d) incl += up; }
+            if (lane == 63) wave_t[w] = incl;
+            __syncthreads();
+            unsigned long long before = carry;
+            for (uint32_t q = 0; q < w; ++q) before += wave_t[q];
+            if (k < P.m) P.offs[c * m1 + k] = before + incl - v;
+            __syncthreads();
+            if (threadIdx.x == 255) carry = before + incl;
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) { P.offs[c * m1 + P.m] = carry; P.totals[c] = carry; }
+        __syncthreads();
+    }
+}
+// a workgroup per window: the arenas (the flags go onto the column bytes once the whole window's bytes are written)
+__global__ __launch_bounds__(256) void wwin_emit_kernel(const WideWinParams P) {
+    for (uint32_t k = blockIdx.x; k < P.m; k += gridDim.x) {
+        wwin_emit_copy(P, k, threadIdx.x, 256u);
+        __syncthreads();
+        wwin_emit_patch(P, k, threadIdx.x, 256u);
+    }
+}
+__global__ __launch_bounds__(256) void wwin_keys_kernel(const WideWinParams P, const int second) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= P.m) return;
+    if (second) wwin_key2_one(P, k); else wwin_key_one(P, k);
+}
+
+int hip_wide_windows(const WideWinParams& P, int what, uint32_t compute_units, hipStream_t st) {
+    if (what == WW_RUN_CLASSIFY) {
+        if (!P.n) return VGK_OK;
+        hipLaunchKernelGGL(wwin_classify_kernel, dim3((P.n + 255) / 256), dim3(256), 0, st, P);
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    if (!P.m) return VGK_OK;
+    const uint32_t per_window = P.m < compute_units * 8u ? P.m : compute_units * 8u;
+    switch (what) {
+        case WW_RUN_NODES:   hipLaunchKernelGGL(wwin_nodes_kernel, dim3(per_window), dim3(256), 0, st, P); break;
+        case WW_RUN_OFFSETS: hipLaunchKernelGGL(wwin_offsets_kernel, dim3(1), dim3(256), 0, st, P); break;
+        case WW_RUN_EMIT:    hipLaunchKernelGGL(wwin_emit_kernel, dim3(per_window), dim3(256), 0, st, P); break;
+        case WW_RUN_KEYS:    hipLaunchKernelGGL(wwin_keys_kernel, dim3((P.m + 255) / 256), dim3(256), 0, st, P, 0); break;
+        case WW_RUN_KEYS2:   hipLaunchKernelGGL(wwin_keys_kernel, dim3((P.m + 255) / 256), dim3(256), 0, st, P, 1); break;
+        default: return VGK_EINVAL;
+    }
+    return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+}
+
 size_t hip_scan_tmp_bytes(uint32_t n) {
     size_t b = 0;
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, n, (hipStream_t)0);

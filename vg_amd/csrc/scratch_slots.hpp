@@ -47,6 +47,11 @@ enum Slot : int {
     // indel; per anchor the group counts, their prefix sums and the scatter's cursors; the groups; the error flag; the table and the outputs; the slabs
     CITEMS_PROBS, CITEMS_CAND_OFF, CITEMS_ANCHORS, CITEMS_CANDS, CITEMS_JUMP, CITEMS_IDS, CITEMS_INDEL, CITEMS_COUNT, CITEMS_FIRST, CITEMS_CURSOR, CITEMS_GROUPED,
     CITEMS_FLAGS, CITEMS_TSCORE, CITEMS_TSOURCE, CITEMS_CHAINS, CITEMS_NCHAINS, CITEMS_ITEMS, CITEMS_REC_RIGHT, CITEMS_REC_LEFT, CITEMS_SLAB,
+    // ---- gssw_wide_window_api.cpp (nothing stays): the call's problems, reads and verdicts; a sub-batch's windows, per-node temporaries, sizes, their
+    // sums, the order's keys; the results and ops packed for the way back.  The arenas the wide kernels read are the WIDE_* buffers (aliases below)
+    WIDEWIN_PROBLEMS, WIDEWIN_READS, WIDEWIN_META, WIDEWIN_SUB, WIDEWIN_STORE, WIDEWIN_NODE_FLAGS, WIDEWIN_SLOT_AT, WIDEWIN_PRED_AT, WIDEWIN_WIN_SLOTS,
+    WIDEWIN_SIZES, WIDEWIN_OFFS, WIDEWIN_KEY, WIDEWIN_IDX, WIDEWIN_KEY_SORTED, WIDEWIN_IDX_SORTED, WIDEWIN_KEY2, WIDEWIN_OPS_OFFS, WIDEWIN_OPS_SUMS,
+    WIDEWIN_RES_OUT, WIDEWIN_OPS_OUT,
     SLOT_COUNT,                        // sizes vgk_ctx::scratch; only aliases follow
 
     // ---- deliberate sharing: a second name for a buffer above, so that a context which uses both paths keeps one set of buffers in HBM.
@@ -60,5 +65,9 @@ enum Slot : int {
     BKBEST_POOL = MULTI_PINNING, BKBEST_ORDER = MULTI_POOL, BKBEST_SP_OFF = MULTI_ORDER, BKBEST_SP_LEN = MULTI_RESULTS, BKBEST_PREFIX = MULTI_N_ALIGNMENTS,
     BKBEST_HOST_ONLY = MULTI_STATUS, BKBEST_RESULTS = MULTI_OPS, BKBEST_N_ALIGNMENTS = MULTI_OPS_OFF, BKBEST_OPS = MULTI_OFFS, BKBEST_OPS_OFF = MULTI_SUMS,
     BKBEST_STATUS = MULTI_PRES, BKBEST_OFFS = MULTI_POPS,
+    // the wide window route over the wide route's arenas: both feed the same kernels
+    WIDEWIN_PROBS = WIDE_PROBS, WIDEWIN_ORDER = WIDE_ORDER, WIDEWIN_COLINFO = WIDE_COLINFO, WIDEWIN_PROF = WIDE_PROF, WIDEWIN_NODES = WIDE_NODES,
+    WIDEWIN_PREDS = WIDE_PREDS, WIDEWIN_SCRATCH = WIDE_SCRATCH, WIDEWIN_CARRY = WIDE_CARRY, WIDEWIN_TB = WIDE_TB, WIDEWIN_BEST = WIDE_BEST,
+    WIDEWIN_RESULTS = WIDE_RESULTS, WIDEWIN_OPS = WIDE_OPS,
 };
 constexpr Slot operator+(Slot base, int k) { return (Slot)((int)base + k); }      // a buffer of a run: its first name + the family's index

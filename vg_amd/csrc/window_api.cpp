@@ -18,6 +18,7 @@
 #include "batch.hpp"
 #include "dgraph.hpp"
 #include "host_parallel.hpp"
+#include "staged_upload.hpp"
 
 
 namespace {
@@ -221,22 +222,7 @@ int vgk_pack_windows_impl(vgk_ctx* ctx, const vgk_dgraph* dg, const char* reads,
         *tz = zero;
         if ((rc = be->upload_side(W.totals, tz, sizeof(WinTotals)))) return fail(rc);
     }
-    auto staged_upload = [&](int slot, void* dst, const void* src, uint64_t bytes) -> int {
-        if (!bytes) return VGK_OK;
-        uint8_t* st = (uint8_t*)lease.s->get(slot, bytes);
-        if (!st) return VGK_ENOMEM;
-        const uint64_t SLICE = 16ull << 20, PIECE = 256ull << 10;
-        for (uint64_t at = 0; at < bytes; at += SLICE) {
-            const uint64_t len = std::min(SLICE, bytes - at);
-            parallel_tasks((uint32_t)((len + PIECE - 1) / PIECE), [&](uint32_t c) {
-                const uint64_t o = at + (uint64_t)c * PIECE;
-                std::memcpy(st + o, (const uint8_t*)src + o, (size_t)std::min(PIECE, at + len - o));
-            });
-            const int e = be->upload_side((uint8_t*)dst + at, st + at, len);
-            if (e) return e;
-        }
-        return VGK_OK;
-    };
+    auto staged_upload = [&](int slot, void* dst, const void* src, uint64_t bytes) -> int { return ::staged_upload(be, *lease.s, slot, dst, src, bytes); };
     if (!on_device && (rc = staged_upload(1, (void*)W.problems, problems, (uint64_t)n * sizeof(vgk_window_problem)))) return fail(rc);
     if (extensions && (rc = staged_upload(3, (void*)W.ext, extensions, (uint64_t)n * sizeof(WinExt)))) return fail(rc);
     lap("problems staged");
