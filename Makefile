@@ -76,3 +76,13 @@ widewin: tests/emu/libvgamd_widewin.so
 tests/emu/libvgamd_widewin.so: tests/emu/wide_windows_driver.cpp $(LIB_HDRS)
 	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -shared -o $@ $<
 .PHONY: widewin
+
+# test-only: the serial form of the device rule that makes chaining anchors from seeds and gapless extensions (extension_anchors_device.hpp:
+# ea_problem_one) behind one C call, and the same as a program of its own under the host sanitizers
+extanchors: tests/emu/libvgamd_extanchors.so
+tests/emu/libvgamd_extanchors.so: tests/emu/extension_anchors_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -shared -o $@ $<
+extanchors_san: tests/emu/extension_anchors_san
+tests/emu/extension_anchors_san: tests/emu/extension_anchors_driver.cpp $(LIB_HDRS)
+	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -DEA_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+.PHONY: extanchors extanchors_san

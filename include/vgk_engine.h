@@ -127,6 +127,59 @@ int vgk_chain_items_limits(uint32_t out[4]);
 /* Device time (ms) of the last vgk_chain_items call on this context: legality + grouping | DP | traceback */
 int vgk_chain_items_last_ms(vgk_ctx* ctx, double ms[3]);
 
+/* ---- anchors for chaining, from seeds and their gapless extensions ---------------------------------------------------------------------------
+ * The step of MinimizerMapper::map_from_chains between vgk_gapless_extend and vgk_chain_items (src/minimizer_mapper_from_chains.cpp:1380-1596),
+ * for thousands of (read, tree) problems per call: every seed's own anchor (to_anchor, :3978-4038); the seeds each extension contains
+ * (extend_seed_group, src/minimizer_mapper.cpp:4881-5000 over for_each_read_interval, src/gbwt_extender.cpp:23-39); the full-length shortcut
+ * (:1408-1464); the extensions in score order, each cut into read intervals around its mismatches (find_anchor_intervals, :480-706), every interval
+ * welded from its first and last unused seed into one composite anchor (to_anchor, :4040-4081); sort_anchor_indexes.  No distance index and no zip
+ * code is read.  The rule is the host shim's (vg_amd/host/extension_anchors.cpp), byte for byte.
+ *
+ * In: problem p's seeds are seeds[seed_off[p] .. seed_off[p + 1]) — node and diff exactly the vgk_seed the same seed gives vgk_gapless_extend,
+ * stapled = Minimizer::pin_offset() (src/minimizer_mapper.hpp:596: a forward minimizer's first read base, a reverse one's last), length = k,
+ * paths = the seed's haplotype flags; the seed's graph offset is stapled - diff.  Its extensions are extensions[ext_off[p] .. ext_off[p + 1]) as
+ * vgk_gapless_extend wrote them WITHOUT VGK_GAPLESS_TRIM (the reference extends with trim == false here, src/minimizer_mapper.cpp:4863), with the
+ * `nodes` and `mismatches` arrays they index; full_length[p] = vgk_gapless_result.full_length of the set.  match / mismatch: the plain scorer's
+ * (a quality-adjusted context: VGK_EUNSUPPORTED).  VGK_ANCHORS_FROM_SEEDS in `flags` is do_gapless_extension == false: the anchors are the seed
+ * anchors, sorted; ext_off and what follows it may then be NULL.
+ *
+ * Out: problem p's anchors are anchors[anchor_off[p] .. anchor_off[p + 1]) in sort_anchor_indexes' order — vgk_chain_items takes anchor_off and
+ * anchors unchanged — and origins[] beside them: the first and last seed welded (numbers within the problem), n_seq = 1 or 2 seeds to paste into the
+ * chain (extension_seed_sequences, :1575-1580), the seeds the anchor stands for in represented[rep_begin .. rep_begin + n_rep) (stapled order),
+ * the extension it was cut from (number within the problem; UINT32_MAX in the seeds-only mode) and its read interval.  Problem p's stretch of
+ * `represented` is rep_off[p] .. rep_off[p + 1].  status[p]: VGK_ANCHORS_FULL_LENGTH when the shortcut applies — the set is
+ * full_length_extensions and some extension is full on both sides with at most default_max_extension_mismatches mismatches: no anchors then, and
+ * the problem's stretch of `represented` lists those extensions' numbers instead, ascending.
+ * Room: anchor_off, rep_off n_problems + 1; status n_problems; anchors / origins cap_anchors; represented cap_rep.  VGK_EOPS when either is too
+ * small, with written[0] = the anchors and written[1] = the entries of `represented` there are (call with both 0 to size); never more than the
+ * seeds, resp. the seeds plus the extensions, of the call.  A seed is used by one anchor at most.
+ *
+ * Ties the reference leaves open are fixed here [PARITY-UNPINNED]: seeds of one diagonal with equal stapled base by seed number (std::sort);
+ * extensions of equal score by number (sort_permutation); anchors with equal read start and end in order of creation (std::sort).  Margins are
+ * uint32 and wrap as the reference's size_t does when a reverse seed's minimizer begins before its interval.
+ *
+ * VGK_EINVAL: offsets that do not ascend from 0; a seed whose graph offset lies outside its node, of length 0, with is_reverse above 1, a reverse
+ * seed stapled before base length - 1, stapled or length so large that a read position leaves int32; an extension whose path or mismatches leave
+ * the arrays, whose read interval is empty or whose path is; mismatches not ascending inside the read interval; match or mismatch negative.
+ * VGK_ETOOBIG: more than 2^32 - 16 seeds, extensions, path nodes or mismatches; or the problems' seeds x extensions summing above that (the bound on the
+ * extensions' seed lists: split the call). */
+typedef struct vgk_anchor_seed { uint32_t node; int32_t diff; uint32_t stapled; uint16_t length; uint16_t is_reverse; uint64_t paths; } vgk_anchor_seed;      /* 24 B */
+typedef struct vgk_anchor_origin { uint32_t seed_first, seed_last, n_seq, rep_begin, n_rep, extension, read_begin, read_end; } vgk_anchor_origin;              /* 32 B */
+#define VGK_ANCHORS_FROM_SEEDS  1u      /* in flags */
+#define VGK_ANCHORS_FULL_LENGTH 1u      /* in status[p] */
+int vgk_extension_anchors(vgk_ctx* ctx, const vgk_haplo* index, int32_t match, int32_t mismatch, uint32_t flags, uint32_t default_max_extension_mismatches,
+                          uint32_t n_problems, const uint64_t* seed_off, const vgk_anchor_seed* seeds,
+                          const uint64_t* ext_off, const vgk_extension* extensions, const uint32_t* full_length /* [n] */,
+                          const uint32_t* nodes, size_t n_nodes, const uint32_t* mismatches, size_t n_mismatches,
+                          uint64_t* anchor_off /* [n + 1] */, vgk_chain_anchor* anchors, vgk_anchor_origin* origins, size_t cap_anchors,
+                          uint64_t* rep_off /* [n + 1] */, uint32_t* represented, size_t cap_rep, uint32_t* status /* [n] */, size_t written[2]);
+/* out[0] = seeds of a problem whose used flags and sort keys fit LDS (larger problems run over a slab in HBM), out[1] = lanes per problem,
+ * out[2] = extensions of a problem whose order fits LDS, out[3] = 0 (reserved).  Needs no context. */
+int vgk_extension_anchors_limits(uint32_t out[4]);
+/* Device time (ms) of the last vgk_extension_anchors call on this context: seed anchors + diagonal sort | the extensions' seed lists | the
+ * order-dependent part, the sort and the write-out */
+int vgk_extension_anchors_last_ms(vgk_ctx* ctx, double ms[3]);
+
 /* ---- windows of the resident graph, of any read length: the wide route on the device ------------------------------------------------------
  * vgk_gssw_pack_windows (vgk.h) takes what the packed kernels take: at most 1024 DP rows, scores inside 11 bits; a longer window fails the whole
  * pack with VGK_ETOOLONG.  This one-call entry takes windows of any read length and scoring and answers every problem in its own status, as

@@ -16,6 +16,7 @@ DEFAULT_LIB = os.path.join(_HERE, "libvgamd.so")
 
 VGK_OK = 0
 VGK_EINVAL, VGK_ENODEV, VGK_ENOMEM, VGK_ETOOLONG, VGK_EOVERFLOW, VGK_EOPS = -1, -2, -3, -4, -5, -6      # include/vgk.h
+VGK_ETOOBIG, VGK_ENOBAND, VGK_EUNSUPPORTED = -7, -8, -9
 VGK_GSSW_LOCAL = 0
 VGK_GSSW_PINNED = 1
 VGK_XDROP_PINNED = 2
@@ -122,6 +123,46 @@ def chain_items_call(fn, head, scheme, anchor_off, anchors, cand_off, candidates
         out["chains"] = out["chains"][:int(out["chain_off"][-1])]
         for name in ("items", "rec_right", "rec_left", "table_source", "table_score"):
             out[name] = out[name][:len(anchors)]
+    return rc, out
+
+
+# vgk_extension_anchors (include/vgk_engine.h): seeds in, chaining anchors and where they come from out
+ANCHOR_SEED_DT = np.dtype([("node", "<u4"), ("diff", "<i4"), ("stapled", "<u4"), ("length", "<u2"), ("is_reverse", "<u2"), ("paths", "<u8")])
+ANCHOR_ORIGIN_DT = np.dtype([("seed_first", "<u4"), ("seed_last", "<u4"), ("n_seq", "<u4"), ("rep_begin", "<u4"), ("n_rep", "<u4"), ("extension", "<u4"),
+                             ("read_begin", "<u4"), ("read_end", "<u4")])
+assert ANCHOR_SEED_DT.itemsize == 24 and ANCHOR_ORIGIN_DT.itemsize == 32
+VGK_ANCHORS_FROM_SEEDS = 1
+VGK_ANCHORS_FULL_LENGTH = 1
+ANCHORS_NO_EXTENSION = 0xffffffff
+
+
+def extension_anchors_call(fn, head, match, mismatch, flags, max_mismatches, seed_off, seeds, ext_off=None, extensions=None, full_length=None, nodes=None, mismatches=None,
+                           tail=(), caps=None):
+    """one call with vgk_extension_anchors' arguments (the engine's, the host shim's vgh_extension_anchors, the serial lane code's): head / tail = ctypes
+    values the function takes before `match` / behind `written`.  caps = (anchors, represented): the room offered (default: the call's bounds, so one call
+    does) -> (rc, dict(anchor_off, anchors, origins, rep_off, represented, status, written))"""
+    soff = np.ascontiguousarray(seed_off, dtype=np.uint64); n = len(soff) - 1
+    seeds = np.ascontiguousarray(seeds, dtype=ANCHOR_SEED_DT)
+    eoff = None if ext_off is None else np.ascontiguousarray(ext_off, dtype=np.uint64)
+    ext = None if extensions is None else np.ascontiguousarray(extensions, dtype=EXT_DT)
+    full = None if full_length is None else np.ascontiguousarray(full_length, dtype=np.uint32)
+    nod = np.zeros(0, dtype=np.uint32) if nodes is None else np.ascontiguousarray(nodes, dtype=np.uint32)
+    mis = np.zeros(0, dtype=np.uint32) if mismatches is None else np.ascontiguousarray(mismatches, dtype=np.uint32)
+    cap_a, cap_r = caps if caps is not None else (len(seeds), len(seeds) + (0 if ext is None else len(ext)))
+    out = dict(anchor_off=np.zeros(n + 1, dtype=np.uint64), rep_off=np.zeros(n + 1, dtype=np.uint64), status=np.zeros(max(n, 1), dtype=np.uint32),
+               anchors=np.zeros(max(cap_a, 1), dtype=CHAIN_ANCHOR_DT), origins=np.zeros(max(cap_a, 1), dtype=ANCHOR_ORIGIN_DT), represented=np.zeros(max(cap_r, 1), dtype=np.uint32))
+    written = (ctypes.c_size_t * 2)()
+    ptr = lambda a: None if a is None or not len(a) else a.ctypes.data
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t] \
+        + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p] + [type(t) for t in tail]
+    rc = fn(*head, int(match), int(mismatch), int(flags), int(max_mismatches), n, soff.ctypes.data, ptr(seeds), None if eoff is None else eoff.ctypes.data, ptr(ext), ptr(full),
+            ptr(nod), len(nod), ptr(mis), len(mis), out["anchor_off"].ctypes.data, out["anchors"].ctypes.data, out["origins"].ctypes.data, cap_a,
+            out["rep_off"].ctypes.data, out["represented"].ctypes.data, cap_r, out["status"].ctypes.data, written, *tail)
+    out["written"] = (int(written[0]), int(written[1]))
+    out["status"] = out["status"][:n]
+    if rc == VGK_OK:
+        out["anchors"] = out["anchors"][:out["written"][0]]; out["origins"] = out["origins"][:out["written"][0]]; out["represented"] = out["represented"][:out["written"][1]]
     return rc, out
 
 
@@ -720,6 +761,30 @@ class Engine:
         ms = (ctypes.c_double * 3)()
         self.lib.vgk_chain_items_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._check(self.lib.vgk_chain_items_last_ms(self.h, ms), "vgk_chain_items_last_ms")
+        return tuple(float(x) for x in ms)
+
+    def extension_anchors(self, index, seed_off, seeds, ext_off=None, extensions=None, full_length=None, nodes=None, mismatches=None, match=1, mismatch=4,
+                          default_max_extension_mismatches=4, from_seeds=False, caps=None):
+        """vgk_extension_anchors (include/vgk_engine.h): the anchors vgk_chain_items takes, from seeds (ANCHOR_SEED_DT) and the extensions vgk_gapless_extend
+        wrote for them without trimming (EXT_DT with their nodes and mismatches; full_length = GAPLESS_RESULT_DT's per problem).  from_seeds: the seed anchors,
+        sorted (do_gapless_extension == false).  caps = (anchors, represented) offers less room than the call's bounds: VgkError on VGK_EOPS unless enough.
+        -> dict(anchor_off, anchors CHAIN_ANCHOR_DT, origins ANCHOR_ORIGIN_DT, rep_off, represented, status, written)"""
+        rc, out = extension_anchors_call(self.lib.vgk_extension_anchors, (self.h, index.h), match, mismatch,
+                                         VGK_ANCHORS_FROM_SEEDS if from_seeds else 0, default_max_extension_mismatches, seed_off, seeds, ext_off, extensions, full_length, nodes, mismatches, caps=caps)
+        self._check(rc, "vgk_extension_anchors")
+        return out
+
+    def extension_anchors_limits(self):
+        """-> (seeds of a problem whose working arrays fit LDS, lanes per problem, extensions of a problem whose order fits LDS, 0)"""
+        out = (ctypes.c_uint32 * 4)()
+        self._check(self.lib.vgk_extension_anchors_limits(out), "vgk_extension_anchors_limits")
+        return tuple(int(x) for x in out)
+
+    def extension_anchors_last_ms(self):
+        """device time of the last extension_anchors call: (seed anchors + diagonal sort, the extensions' seed lists, the order-dependent part + sort) in ms"""
+        ms = (ctypes.c_double * 3)()
+        self.lib.vgk_extension_anchors_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_extension_anchors_last_ms(self.h, ms), "vgk_extension_anchors_last_ms")
         return tuple(float(x) for x in ms)
 
     def minimizer_last_ms(self):

@@ -23,6 +23,7 @@
 #include "rescue_requests_device.hpp"
 #include "chain_device.hpp"
 #include "chain_items_device.hpp"
+#include "extension_anchors_device.hpp"
 
 namespace vgk {
 
@@ -163,6 +164,10 @@ public:
     // one stage of vgk_chain_items (chain_items_device.hpp: CI_RUN_*), asynchronous on the main stream: a lane per candidate (legality, scatter), or
     // `blocks` wavefronts over the problems p.ids[0 .. p.n) (DP, traceback): a problem each in LDS, or (p.slab) striding over them with a slab each.  Optional
     virtual int   run_chain_items(const CiParams& p, int what, uint32_t blocks) { (void)p; (void)what; (void)blocks; return VGK_EUNSUPPORTED; }
+    // one stage of vgk_extension_anchors (extension_anchors_device.hpp: EA_RUN_*), asynchronous on the main stream: a lane per seed (SEEDS) or per
+    // extension (COUNT, EMIT), or `blocks` wavefronts over the problems p.ids[0 .. p.n) (SORT, ANCHORS): a problem each in LDS, or (p.slab) striding over
+    // them with a slab each.  Optional
+    virtual int   run_extension_anchors(const EaParams& p, int what, uint32_t blocks) { (void)p; (void)what; (void)blocks; return VGK_EUNSUPPORTED; }
     virtual int   run_tail(const TailParams& p, uint32_t threads) = 0;
     virtual int   run_tail_stage(const TStageParams& p, int what) = 0;     // one of the per-item stages of vgk_tail_stage (tail_device.hpp: TS_*)
     virtual int   run_rescue_requests(const RqParams& p, int what) = 0;    // one of the per-pair stages of vgk_rescue_requests (rescue_requests_device.hpp: RQ_*)

@@ -1181,6 +1181,88 @@ __global__ void __launch_bounds__(64) chain_items_trace_slab_kernel(const CiPara
         __syncthreads();
     }
 }
+// ---- anchors from seeds and gapless extensions (extension_anchors_device.hpp: ea_problem_one is the rule and the checker).  A lane per seed makes
+// its anchor; a wavefront per problem puts the problem's seeds in diagonal order (a bitonic sort of seed numbers: LDS, or the slab); a lane per extension
+// walks its path and counts, then — behind the prefix sums — lists the seeds it contains; a wavefront per problem does what depends on the order of the
+// extensions: their order (bitonic), the sweep with its used flags (lane 0: ea_extension, the very code of the serial statement), the anchors' order
+// (bitonic) and the write-out across the lanes.
+__global__ void __launch_bounds__(256) extension_anchors_seeds_kernel(const EaParams P) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= P.n_seeds) return;
+    vgk_chain_anchor a;
+    if (ea_seed_anchor(P.seeds[i], P.n_oriented, P.node_tab, P.match, &a)) P.seed_anchor[i] = a;
+    else atomicOr(P.flags, (uint32_t)EA_BAD_SEED);
+}
+__device__ void ea_sort_problem(const EaParams& P, uint32_t p, uint32_t* order, uint32_t lane) {
+    const EaProb q = P.probs[p];
+    if (!q.n_seeds || !q.n_ext) return;
+    const vgk_anchor_seed* s = P.seeds + q.s_off;
+    uint32_t np = 1; while (np < q.n_seeds) np <<= 1;
+    for (uint32_t i = lane; i < np; i += 64) order[i] = i < q.n_seeds ? i : EA_NONE;
+    __syncthreads();
+    ci_bitonic<uint32_t>(order, np, lane, [&](uint32_t x, uint32_t y) { return ea_diag_before(s, x, y); });
+    for (uint32_t i = lane; i < q.n_seeds; i += 64) P.sorted[q.s_off + i] = order[i];
+}
+__global__ void __launch_bounds__(64) extension_anchors_sort_kernel(const EaParams P) {
+    ea_sort_problem(P, P.ids[blockIdx.x], (uint32_t*)ci_lds, threadIdx.x);
+}
+__global__ void __launch_bounds__(64) extension_anchors_sort_slab_kernel(const EaParams P) {
+    uint32_t* order = (uint32_t*)(P.slab + (uint64_t)blockIdx.x * P.slab_stride);
+    for (uint32_t i = blockIdx.x; i < P.n; i += gridDim.x) { ea_sort_problem(P, P.ids[i], order, threadIdx.x); __syncthreads(); }
+}
+__global__ void __launch_bounds__(256) extension_anchors_lists_kernel(const EaParams P, const int emit) {
+    const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (x >= P.n_ext) return;
+    const EaProb q = P.probs[P.prob_of_ext[x]];
+    if (emit) {
+        uint32_t* list = P.ext_seeds + P.ext_first[x]; uint32_t at = 0;
+        ea_ext_seeds(P.ext[x], P.nodes, P.node_tab, P.seeds + q.s_off, P.sorted + q.s_off, q.n_seeds, [&](uint32_t i) { list[at++] = i; });
+    } else P.ext_count[x] = ea_ext_seeds(P.ext[x], P.nodes, P.node_tab, P.seeds + q.s_off, P.sorted + q.s_off, q.n_seeds, [](uint32_t) {});
+}
+__device__ void ea_anchors_problem(const EaParams& P, uint32_t p, uint32_t* order, uint32_t* used, uint32_t lane) {
+    const EaProb q = P.probs[p];
+    const vgk_anchor_seed* s = P.seeds + q.s_off; const vgk_extension* e = P.ext + q.e_off; const vgk_chain_anchor* sa = P.seed_anchor + q.s_off;
+    vgk_chain_anchor* made = P.made + q.s_off; vgk_anchor_origin* origin = P.made_origin + q.s_off; uint32_t* rep = P.rep + q.s_off + q.e_off;
+    uint32_t n_made = 0, n_rep = 0;
+    if (P.from_seeds) {
+        for (uint32_t i = lane; i < q.n_seeds; i += 64) ea_from_seed(sa[i], i, made, origin, rep);
+        n_made = n_rep = q.n_seeds;
+    } else {
+        uint32_t n_full = 0;
+        if (lane == 0) n_full = ea_full_length(q, e, P.max_mismatches, rep);
+        n_full = (uint32_t)__shfl((int)n_full, 0);
+        if (n_full) { if (lane == 0) { P.status[p] = VGK_ANCHORS_FULL_LENGTH; P.n_anchors[p] = 0u; P.n_rep[p] = n_full; } return; }
+        uint32_t np = 1; while (np < q.n_ext) np <<= 1;
+        for (uint32_t i = lane; i < np; i += 64) order[i] = i < q.n_ext ? i : EA_NONE;
+        for (uint32_t w = lane; w < q.n_seeds / 32u + 1u; w += 64) used[w] = 0u;
+        __syncthreads();
+        ci_bitonic<uint32_t>(order, np, lane, [&](uint32_t x, uint32_t y) { return ea_ext_before(e, x, y); });
+        if (lane == 0) {
+            EaOut out{made, origin, rep, 0u, 0u};
+            for (uint32_t k = 0; k < q.n_ext; ++k) {
+                const uint32_t x = order[k], l0 = P.ext_first[q.e_off + x], l1 = P.ext_first[q.e_off + x + 1];
+                ea_extension(e[x], x, P.mism + e[x].mism_begin, P.ext_seeds + l0, l1 - l0, s, sa, used, P.match, P.mismatch, out);
+            }
+            n_made = out.n_made; n_rep = out.n_rep;
+        }
+        n_made = (uint32_t)__shfl((int)n_made, 0); n_rep = (uint32_t)__shfl((int)n_rep, 0);
+    }
+    __syncthreads();
+    uint32_t np = 1; while (np < n_made) np <<= 1;
+    for (uint32_t i = lane; i < np; i += 64) order[i] = i < n_made ? i : EA_NONE;
+    __syncthreads();
+    ci_bitonic<uint32_t>(order, np, lane, [&](uint32_t x, uint32_t y) { return ea_anchor_before(made, x, y); });
+    for (uint32_t k = lane; k < n_made; k += 64) { const uint32_t from = order[k]; P.anchors[q.s_off + k] = made[from]; P.origins[q.s_off + k] = origin[from]; }
+    if (lane == 0) { P.status[p] = 0u; P.n_anchors[p] = n_made; P.n_rep[p] = n_rep; }
+}
+__global__ void __launch_bounds__(64) extension_anchors_kernel(const EaParams P) {
+    uint32_t* order = (uint32_t*)ci_lds;
+    ea_anchors_problem(P, P.ids[blockIdx.x], order, order + P.lds_np, threadIdx.x);
+}
+__global__ void __launch_bounds__(64) extension_anchors_slab_kernel(const EaParams P) {
+    uint32_t* order = (uint32_t*)(P.slab + (uint64_t)blockIdx.x * P.slab_stride);
+    for (uint32_t i = blockIdx.x; i < P.n; i += gridDim.x) { ea_anchors_problem(P, P.ids[i], order, order + P.slab_np, threadIdx.x); __syncthreads(); }
+}
 // ---- one Path per read (chain_device.hpp): a lane per read for the bounds and the composition, a wavefront per read for the dense copy
 __global__ void __launch_bounds__(64) chain_stitch_kernel(const CsParams P, const int what) {
     cs_one(P, what, blockIdx.x * 64 + threadIdx.x);
@@ -2022,6 +2104,28 @@ public:
                 else hipLaunchKernelGGL(chain_items_trace_kernel, dim3(blocks), dim3(64), ci_trace_lds_bytes(p.lds_np), stream, p);
             } else return VGK_EINVAL;
         }
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_extension_anchors(const EaParams& p, int what, uint32_t blocks) override {
+        hipSetDevice(dev);
+        if (what == EA_RUN_SEEDS) {
+            if (!p.n_seeds) return VGK_OK;
+            hipLaunchKernelGGL(extension_anchors_seeds_kernel, dim3((uint32_t)((p.n_seeds + 255) / 256)), dim3(256), 0, stream, p);
+        } else if (what == EA_RUN_COUNT || what == EA_RUN_EMIT) {
+            if (!p.n_ext) return VGK_OK;
+            hipLaunchKernelGGL(extension_anchors_lists_kernel, dim3((uint32_t)((p.n_ext + 255) / 256)), dim3(256), 0, stream, p, what == EA_RUN_EMIT ? 1 : 0);
+        } else if (what == EA_RUN_SORT || what == EA_RUN_ANCHORS) {
+            if (!blocks) return VGK_OK;
+            if (!p.slab && (p.lds_np > std::max(EA_LDS_SEEDS, EA_LDS_EXT) || (p.lds_np & (p.lds_np - 1u)))) return VGK_EINVAL;
+            const uint32_t lds = (uint32_t)ea_work_bytes(p.lds_np, EA_LDS_SEEDS);
+            if (what == EA_RUN_SORT) {
+                if (p.slab) hipLaunchKernelGGL(extension_anchors_sort_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
+                else hipLaunchKernelGGL(extension_anchors_sort_kernel, dim3(blocks), dim3(64), lds, stream, p);
+            } else {
+                if (p.slab) hipLaunchKernelGGL(extension_anchors_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
+                else hipLaunchKernelGGL(extension_anchors_kernel, dim3(blocks), dim3(64), lds, stream, p);
+            }
+        } else return VGK_EINVAL;
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
     int run_minimizer_choose(const MzChooseParams& p, uint32_t blocks) override {

@@ -105,6 +105,7 @@ struct vgk_ctx {
     double minimizer_ms = 0;       // device time of the last vgk_minimizer_seeds call
     double minimizer_choose_ms = 0; // ... and of the choice kernels of the last vgk_minimizer_choose / vgk_minimizer_find_seeds call
     double chain_items_ms[3] = {0, 0, 0};   // last vgk_chain_items: legality + grouping | DP | traceback
+    double extension_anchors_ms[3] = {0, 0, 0};   // last vgk_extension_anchors: seed anchors + diagonal sort | the extensions' seed lists | anchors
     double tail_stage_ms[4] = {0, 0, 0, 0};   // last vgk_tail_stage: tails derived | forest | windows packed | kernels + totals
     double tail_ms = 0;            // device time of the last vgk_tail_forest call
     // the last batch of either call stays resident in the cached device buffers: what a re-run needs to launch it again

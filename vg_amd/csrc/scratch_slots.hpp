@@ -47,6 +47,11 @@ enum Slot : int {
     // indel; per anchor the group counts, their prefix sums and the scatter's cursors; the groups; the error flag; the table and the outputs; the slabs
     CITEMS_PROBS, CITEMS_CAND_OFF, CITEMS_ANCHORS, CITEMS_CANDS, CITEMS_JUMP, CITEMS_IDS, CITEMS_INDEL, CITEMS_COUNT, CITEMS_FIRST, CITEMS_CURSOR, CITEMS_GROUPED,
     CITEMS_FLAGS, CITEMS_TSCORE, CITEMS_TSOURCE, CITEMS_CHAINS, CITEMS_NCHAINS, CITEMS_ITEMS, CITEMS_REC_RIGHT, CITEMS_REC_LEFT, CITEMS_SLAB,
+    // ---- extension_anchors_api.cpp (nothing stays): the problems and their inputs (seeds, extensions, path nodes, mismatches, the problem of each
+    // extension), the launch's problem numbers; per seed its anchor and its place in the diagonal order; per extension the number of seeds it contains,
+    // the prefix sums, the lists; the error flag; the anchors as made and sorted with their origins, the represented seeds, the per-problem counts; the slabs
+    EANCH_PROBS, EANCH_SEEDS, EANCH_EXT, EANCH_NODES, EANCH_MISM, EANCH_PROB_OF_EXT, EANCH_IDS, EANCH_SEED_ANCHOR, EANCH_SORTED, EANCH_EXT_COUNT, EANCH_EXT_FIRST,
+    EANCH_EXT_SEEDS, EANCH_FLAGS, EANCH_MADE, EANCH_MADE_ORIGIN, EANCH_ANCHORS, EANCH_ORIGINS, EANCH_REP, EANCH_N_ANCHORS, EANCH_N_REP, EANCH_STATUS, EANCH_SLAB,
     // ---- gssw_wide_window_api.cpp (nothing stays): the call's problems, reads and verdicts; a sub-batch's windows, per-node temporaries, sizes, their
     // sums, the order's keys; the results and ops packed for the way back.  The arenas the wide kernels read are the WIDE_* buffers (aliases below)
     WIDEWIN_PROBLEMS, WIDEWIN_READS, WIDEWIN_META, WIDEWIN_SUB, WIDEWIN_STORE, WIDEWIN_NODE_FLAGS, WIDEWIN_SLOT_AT, WIDEWIN_PRED_AT, WIDEWIN_WIN_SLOTS,

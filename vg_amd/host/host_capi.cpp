@@ -1172,3 +1172,91 @@ int vgh_find_best_chains(const vgk_chain_scheme* scheme, uint32_t n_problems, co
     } catch (std::exception& e) { g_last_error = e.what(); return -1; }
 }
 }  // extern "C"
+
+#include "extension_anchors.hpp"
+extern "C" {
+// find_anchor_intervals alone: intervals[2 k], intervals[2 k + 1] = interval k; -> their number (room for n_seeds intervals is enough), -1 when the shim throws
+int64_t vgh_find_anchor_intervals(uint64_t read_begin, uint64_t read_end, const uint64_t* mismatch_positions, uint64_t n_mismatches, const uint64_t* seed_positions, uint64_t n_seeds,
+                                  uint64_t* intervals, uint64_t cap) {
+    try {
+        const std::vector<size_t> mm(mismatch_positions, mismatch_positions + n_mismatches), sp(seed_positions, seed_positions + n_seeds);
+        const auto found = find_anchor_intervals({(size_t)read_begin, (size_t)read_end}, mm, sp);
+        for (size_t k = 0; k < found.size() && k < cap; ++k) { intervals[2 * k] = found[k].first; intervals[2 * k + 1] = found[k].second; }
+        return (int64_t)found.size();
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+// extension_anchors (extension_anchors.hpp) for a batch of problems, over the flat arrays of the engine's vgk_extension_anchors (include/vgk_engine.h)
+// and with its output layout; oriented_node_length[n_oriented] stands for the index.  Nothing is validated beyond what keeps the arrays' bounds: a
+// malformed call answers -1.  Problems on `threads` host threads (0 = all).
+int vgh_extension_anchors(const uint32_t* oriented_node_length, uint64_t n_oriented, int32_t match, int32_t mismatch, uint32_t flags, uint32_t default_max_extension_mismatches,
+                          uint32_t n_problems, const uint64_t* seed_off, const vgk_anchor_seed* seeds, const uint64_t* ext_off, const vgk_extension* extensions,
+                          const uint32_t* full_length, const uint32_t* nodes, size_t n_nodes, const uint32_t* mismatches, size_t n_mismatches,
+                          uint64_t* anchor_off, vgk_chain_anchor* anchors, vgk_anchor_origin* origins, size_t cap_anchors,
+                          uint64_t* rep_off, uint32_t* represented, size_t cap_rep, uint32_t* status, size_t written[2], int threads) {
+    try {
+        const bool from_seeds = (flags & VGK_ANCHORS_FROM_SEEDS) != 0;
+        std::vector<ExtensionAnchors> results(n_problems);
+        unsigned T = threads > 0 ? (unsigned)threads : std::max(1u, std::thread::hardware_concurrency());
+        T = std::min<unsigned>(T, std::max<uint32_t>(1, n_problems));
+        std::atomic<uint32_t> next{0}; std::atomic<bool> failed{false}; std::string what; std::mutex what_mu;
+        auto work = [&]() {
+            try {
+                std::vector<AnchorSeed> tree_seeds; std::vector<Extension> tree_extensions;
+                for (uint32_t p = next.fetch_add(1); p < n_problems; p = next.fetch_add(1)) {
+                    tree_seeds.clear(); tree_extensions.clear();
+                    for (uint64_t i = seed_off[p]; i < seed_off[p + 1]; ++i) {
+                        const vgk_anchor_seed& y = seeds[i];
+                        if (y.node >= n_oriented || (int64_t)y.stapled - y.diff < 0 || (int64_t)y.stapled - y.diff >= (int64_t)oriented_node_length[y.node]) throw std::runtime_error("a seed outside its node");
+                        AnchorSeed x; x.node = y.node; x.diff = y.diff; x.stapled = y.stapled; x.length = y.length; x.is_reverse = y.is_reverse != 0; x.paths = y.paths;
+                        tree_seeds.push_back(x);
+                    }
+                    if (!from_seeds) for (uint64_t i = ext_off[p]; i < ext_off[p + 1]; ++i) {
+                        const vgk_extension& y = extensions[i];
+                        if ((uint64_t)y.path_begin + y.path_len > n_nodes || (uint64_t)y.mism_begin + y.n_mismatches > n_mismatches) throw std::runtime_error("an extension outside its arrays");
+                        Extension x; x.path.assign(nodes + y.path_begin, nodes + y.path_begin + y.path_len); x.offset = y.offset; x.read_interval = {y.read_begin, y.read_end};
+                        x.mismatch_positions.assign(mismatches + y.mism_begin, mismatches + y.mism_begin + y.n_mismatches); x.left_full = y.left_full != 0; x.right_full = y.right_full != 0;
+                        for (uint32_t node : x.path) if (node >= n_oriented) throw std::runtime_error("an extension's node outside the index");
+                        tree_extensions.push_back(std::move(x));
+                    }
+                    results[p] = extension_anchors(tree_seeds, tree_extensions, !from_seeds && full_length && full_length[p] != 0, oriented_node_length, match, mismatch,
+                                                   default_max_extension_mismatches, !from_seeds);
+                }
+            } catch (std::exception& e) { failed = true; std::lock_guard<std::mutex> lk(what_mu); what = e.what(); }
+        };
+        std::vector<std::thread> pool;
+        for (unsigned t = 1; t < T; ++t) pool.emplace_back(work);
+        work();
+        for (std::thread& t : pool) t.join();
+        if (failed) { g_last_error = what; return -1; }
+        uint64_t n_anchors = 0, n_rep = 0;
+        for (const ExtensionAnchors& r : results) {
+            n_anchors += r.anchors.size(); n_rep += r.full_length_extensions.size();
+            for (const AnchorOrigin& o : r.origins) n_rep += o.represented_seeds.size();
+        }
+        if (written) { written[0] = n_anchors; written[1] = n_rep; }
+        if (n_anchors > cap_anchors || n_rep > cap_rep) return -6;      // VGK_EOPS
+        uint64_t at = 0, rep_at = 0;
+        for (uint32_t p = 0; p < n_problems; ++p) {
+            const ExtensionAnchors& r = results[p];
+            anchor_off[p] = at; rep_off[p] = rep_at; status[p] = r.full_length ? VGK_ANCHORS_FULL_LENGTH : 0u;
+            for (size_t x : r.full_length_extensions) represented[rep_at++] = (uint32_t)x;
+            // the represented seeds lie in order of creation: extension by extension in score order, interval by interval
+            std::vector<size_t> creation(r.anchors.size()); std::vector<uint32_t> rep_begin(r.anchors.size(), 0);
+            for (size_t k = 0; k < creation.size(); ++k) creation[r.origins[k].created] = k;
+            for (size_t k : creation) { rep_begin[k] = (uint32_t)rep_at; for (size_t s : r.origins[k].represented_seeds) represented[rep_at++] = (uint32_t)s; }
+            for (size_t k = 0; k < r.anchors.size(); ++k) {
+                const vgamd::Anchor& x = r.anchors[k]; const AnchorOrigin& o = r.origins[k];
+                vgk_chain_anchor y;
+                y.read_start = (uint32_t)x.start; y.length = (uint32_t)x.size; y.margin_before = (uint32_t)x.margin_before; y.margin_after = (uint32_t)x.margin_after; y.score = x.points;
+                y.start_hint_offset = (uint32_t)x.start_offset; y.end_hint_offset = (uint32_t)x.end_offset; y.base_seed_length = (uint32_t)x.seed_length; y.start_paths = x.start_paths; y.end_paths = x.end_paths;
+                anchors[at] = y;
+                origins[at] = vgk_anchor_origin{(uint32_t)o.represented_seeds.front(), (uint32_t)o.represented_seeds.back(), (uint32_t)o.seed_sequence.size(), rep_begin[k],
+                                                (uint32_t)o.represented_seeds.size(), from_seeds ? 0xffffffffu : (uint32_t)o.extension, (uint32_t)o.interval.first, (uint32_t)o.interval.second};
+                ++at;
+            }
+        }
+        anchor_off[n_problems] = at; rep_off[n_problems] = rep_at;
+        return 0;
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+}  // extern "C"

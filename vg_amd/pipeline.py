@@ -488,6 +488,38 @@ def find_best_chains(eng, problems, scheme=None, read_lookback=None, indel_limit
     return unpack_chains(out, aoff)
 
 
+def extension_anchors(eng, index, problems, match=1, mismatch=4, max_mismatches=4, overlap_threshold=0.8, default_max_extension_mismatches=4, do_gapless_extension=True, extend_with=None):
+    """The anchors of a batch of (read, tree) problems as MinimizerMapper::map_from_chains makes them for chaining (src/minimizer_mapper_from_chains.cpp:
+    1380-1596): vgk_gapless_extend over every problem's seeds WITHOUT trimming (extend_seed_group keeps the seeds of an extension: src/minimizer_mapper.cpp:4863),
+    then vgk_extension_anchors (include/vgk_engine.h) over the extensions where they lie.  problems: dict(reads uint8 flat, read_off, seed_off, seeds
+    ANCHOR_SEED_DT) — one read per problem, as workloads.ExtensionAnchorsWorkload.problems makes them.  A cluster is a set: the extension sees each
+    (node, diagonal) of a problem once.  do_gapless_extension=False: the seed anchors, sorted.  extend_with = (engine, its index): who runs
+    vgk_gapless_extend instead of eng (the CPU oracle, say, for a measurement of the new call alone).  A read the extension refuses (status != 0) has no
+    extensions; `gapless_status` hands the statuses on.
+    -> vgk_extension_anchors' answer (anchor_off and anchors go to vgk_chain_items unchanged) plus what it was given: seed_off, seeds, ext_off, extensions,
+    full_length, nodes, mismatches"""
+    seeds = np.ascontiguousarray(problems["seeds"], dtype=capi.ANCHOR_SEED_DT); soff = np.ascontiguousarray(problems["seed_off"], dtype=np.uint64); n = len(soff) - 1
+    given = dict(seed_off=soff, seeds=seeds, ext_off=None, extensions=None, full_length=None, nodes=None, mismatches=None)
+    if do_gapless_extension:
+        of = np.repeat(np.arange(n, dtype=np.int64), np.diff(soff.astype(np.int64)))
+        rows = np.unique(np.stack([of, seeds["node"].astype(np.int64), seeds["diff"].astype(np.int64)], axis=1), axis=0) if len(seeds) else np.zeros((0, 3), dtype=np.int64)
+        cluster = np.zeros(len(rows), dtype=capi.SEED_DT); cluster["node"] = rows[:, 1]; cluster["diff"] = rows[:, 2]
+        coff = np.concatenate([[0], np.cumsum(np.bincount(rows[:, 0], minlength=n))]).astype(np.int64)
+        room = max(1 << 20, 64 * len(cluster))
+        gs = capi.GaplessSet(problems["reads"], problems["read_off"], cluster, coff, max_mismatches, overlap_threshold, trim=False, node_cap=room, mism_cap=room)
+        by, by_index = extend_with or (eng, index)
+        res, ext, nodes, mism = by.gapless_extend(by_index, gs)
+        n_ext = np.where(res["status"] == 0, res["n_ext"], 0).astype(np.int64)
+        eoff = np.concatenate([[0], np.cumsum(n_ext)]).astype(np.uint64)
+        if not ((res["ext_begin"][n_ext > 0] == eoff[:-1][n_ext > 0]).all() and int(eoff[-1]) == len(ext)):
+            raise RuntimeError("vgk_gapless_extend: the sets do not lie in problem order")
+        given.update(ext_off=eoff, extensions=ext.copy(), full_length=res["full_length"].copy(), nodes=nodes.copy(), mismatches=mism.copy(), gapless_status=res["status"].copy())
+    out = eng.extension_anchors(index, soff, seeds, given["ext_off"], given["extensions"], given["full_length"], given["nodes"], given["mismatches"], match, mismatch,
+                                default_max_extension_mismatches, from_seeds=not do_gapless_extension)
+    out.update(given)
+    return out
+
+
 class ChainStage:
     """MinimizerMapper's chain alignment for a batch of reads, in C++ behind one call (vgh_chain_stage): every link through WFAExtender;
     what it declines through align_sequence_between_consistently — the local graph between / beyond the anchors cut out of the haplotype

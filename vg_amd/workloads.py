@@ -1115,3 +1115,36 @@ class ChainItemsWorkload:
             cands["from"] = frm; cands["to"] = to; cands["graph_distance"] = d[frm, to]
             where = np.empty(m, dtype=np.int64); where[order] = np.arange(m)
             self.problems.append((anchors, cands)); self.truth.append(where[:n_planted].tolist())
+
+
+class ExtensionAnchorsWorkload:
+    """What MinimizerMapper::map_from_chains turns into chaining anchors (src/minimizer_mapper_from_chains.cpp:1380-1596), one (read, tree) problem per
+    read: reads off haplotype walks of a variation graph with substitutions — so that their gapless extensions carry mismatches — and, from `problems`,
+    their seeds as the device's own minimizer seeding finds them (pipeline.seed_long_reads, choice="device").  Which seeds form a tree is the caller's: here
+    a read's seeds are one tree."""
+
+    def __init__(self, n_reads, seed=0, read_len=1000, graph_bp=200_000, n_haplotypes=8, k=29, w=11, policy=None):
+        base = GaplessWorkload(n_reads, seed=seed, graph_bp=graph_bp, n_haplotypes=n_haplotypes, read_len=read_len, seeds_per_read=1)
+        self.nodes, self.threads = base.nodes, base.threads
+        self.reads = base.gs.reads; self.read_off = np.arange(n_reads + 1, dtype=np.uint64) * read_len
+        self.n, self.read_len, self.k, self.w, self.policy = n_reads, read_len, k, w, policy
+
+    def problems(self, eng, index=None, choice="device"):
+        """choice: who chooses the minimizers (pipeline.seed_long_reads).  -> dict(reads, read_off, seed_off, seeds ANCHOR_SEED_DT, dropped).  A seed is stapled at its minimizer's first read base, or its last for a
+        reverse minimizer; the seeding reports every seed at the k-mer's first base, so a reverse minimizer that crosses a node end would be stapled
+        beyond the node it is reported on — moving it onto the node of its last base is a walk the seeding does not make, and such seeds are dropped."""
+        from . import pipeline
+        mi = eng.minimizer_index(self.nodes, self.threads, self.k, self.w)
+        found = pipeline.seed_long_reads(eng, mi, self.reads, self.read_off, self.k, policy=self.policy, choice=choice)
+        recs, soff, raw = found["minimizers"], found["seed_off"].astype(np.int64), found["seeds"]
+        per = np.diff(soff)
+        rev = np.repeat((recs["flags"] & capi.MINIMIZER_REVERSE) != 0, per)
+        stapled = np.repeat(recs["offset"].astype(np.int64), per) + np.where(rev, self.k - 1, 0)
+        read_of = np.repeat(np.repeat(np.arange(self.n), np.diff(found["minimizer_off"].astype(np.int64))), per)
+        olen = np.repeat(np.array([len(s) for s in self.nodes], dtype=np.int64), 2)
+        offset = stapled - raw["diff"]
+        keep = (offset >= 0) & (offset < olen[raw["node"]])
+        seeds = np.zeros(int(keep.sum()), dtype=capi.ANCHOR_SEED_DT)
+        seeds["node"] = raw["node"][keep]; seeds["diff"] = raw["diff"][keep]; seeds["stapled"] = stapled[keep]; seeds["length"] = self.k; seeds["is_reverse"] = rev[keep]; seeds["paths"] = 1
+        seed_off = np.concatenate([[0], np.cumsum(np.bincount(read_of[keep], minlength=self.n))]).astype(np.uint64)
+        return dict(reads=self.reads, read_off=self.read_off, seed_off=seed_off, seeds=seeds, dropped=int((~keep).sum()))
