@@ -86,3 +86,13 @@ extanchors_san: tests/emu/extension_anchors_san
 tests/emu/extension_anchors_san: tests/emu/extension_anchors_driver.cpp $(LIB_HDRS)
 	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -DEA_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 .PHONY: extanchors extanchors_san
+
+# test-only: the serial form of the device rule that composes a short read's alignments from its extension set and its tails
+# (read_alignments_device.hpp: ra_read_one) behind one C call, and the same as a program of its own under the host sanitizers
+readaln: tests/emu/libvgamd_readaln.so
+tests/emu/libvgamd_readaln.so: tests/emu/read_alignments_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -shared -o $@ $<
+readaln_san: tests/emu/read_alignments_san
+tests/emu/read_alignments_san: tests/emu/read_alignments_driver.cpp $(LIB_HDRS)
+	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -DRA_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+.PHONY: readaln readaln_san

@@ -180,6 +180,85 @@ int vgk_extension_anchors_limits(uint32_t out[4]);
  * order-dependent part, the sort and the write-out */
 int vgk_extension_anchors_last_ms(vgk_ctx* ctx, double ms[3]);
 
+/* ---- giraffe's alignments of a short read, composed on the device ----------------------------------------------------------------------------
+ * What MinimizerMapper::map_from_extensions makes of an extension set once its tails are aligned (src/minimizer_mapper.cpp:934-1000): for a set
+ * whose full_length is set, one alignment per leading extension that is full on both sides (extension_to_alignment :3905-3914 over
+ * GaplessExtension::to_path, src/gbwt_extender.cpp:119-156); for any other set exactly two, the best and the second best of
+ * find_optimal_tail_alignments (:5369-5622): min_tails, the two Pareto frontiers (:5263-5311, :5397-5419), the extensions in score order through
+ * process_until_threshold_e (src/minimizer_mapper.hpp:1580-1659) with the score-estimate skip (:5453-5479), the totals, the winner and the runner-up
+ * that differs from it at both end nodes (:5545-5590), the tails' Paths as get_best_alignment_against_any_tree returns them (:5626-5743; a left
+ * tail flipped as reverse_complement_path does) and the concatenation by add_to_path (:5318-5367) — no simplify.  No distance index and no zip code
+ * is read.  The rule is stated serially in vg_amd/csrc/read_alignments_device.hpp (ra_read_one), which the kernels call.
+ *
+ * In: read r is reads[read_off[r] .. read_off[r + 1]) as the caller holds it (a base that is not one of ACGT never matches); results[r] its
+ * vgk_gapless_result, with the `extensions`, `nodes` and `mismatches` arrays of the vgk_gapless_extend call; `tails` and `ops` exactly as
+ * vgk_tail_stage_aligned returned them for those extensions (in any order).  An open end without a tail entry, and a tail with n_ops 0, is the soft
+ * clip.  Scores are the context's: match = matrix[0], mismatch = -matrix[1], gap open / extend, full-length bonus; a quality-adjusted context:
+ * VGK_EUNSUPPORTED.
+ *
+ * Out: read r's alignments are alignments[aln_off[r] .. aln_off[r + 1]): VGK_READ_ALN_DIRECT ones in set order, or BEST then SECOND (either may be
+ * empty: score 0, no mappings, extension = UINT32_MAX).  A header begins with the fields of vgk_chain_result, so that mappings and edit runs are
+ * laid out as vgk_chain_stitch's: per mapping {oriented node, offset, edit_begin, n_edits}, ranks = index + 1; per edit length << 2 | VGK_WFA_*.
+ * Every mismatch is a one-base edit of its own, match runs lie between them, soft clips are insertions; inserted and substituted bases are the read's
+ * own.  identity = identity_num / identity_den (0 when identity_den is 0): identity(path) for BEST / SECOND, (len - mismatches) / len for DIRECT.
+ * A read whose input is malformed, or whose gapless result failed, has ONE header with that status and nothing else.
+ * Room: aln_off n + 1; VGK_EOPS when cap_alignments, cap_mappings or cap_edits is too small, with written[0..2] = the alignments, mappings and
+ * edit runs there are (call with all three 0 to size); nothing is written past a capacity.
+ *
+ * [PARITY-UNPINNED] the reference shuffles the extensions that tie for the top score with the read's generator (sort_shuffling_ties,
+ * src/utility.hpp:771-794), whose state depends on everything drawn earlier in the read's life: here ties stay in extension order.  Node ids are
+ * (oriented node >> 1) + 1, so that 0 stays "none yet" as at :5545-5556.  Consecutive ops of a tail on one oriented node are one mapping, until
+ * the node's bases are spent and an M or D op follows: that is a second visit (a self-loop), a mapping of its own at offset 0.
+ *
+ * Per read VGK_EINVAL (the read's one header; the call goes on): ext_begin + n_ext beyond the extensions; a path or mismatch list beyond its array,
+ * an empty path, a node outside the index, offset outside the first node, a read interval that is empty or leaves the read, a path that does not
+ * hold the interval's bases exactly; mismatches outside [read_begin, read_end) or not ascending; left_full / right_full that disagree with the
+ * interval; full_length set on a set whose first extension is not full; a tail on a closed end, a second tail for one end, read_begin / read_end
+ * that are not the open end's, ops beyond their array, an op of length 0, of an unknown kind or on a node outside the index, ops that spend more
+ * read bases than the tail has or more bases of a node than it has.  For the call: VGK_EINVAL offsets that do not ascend from 0, a tail whose `ext`
+ * is beyond the extensions, unknown flags, window_length 0; VGK_ETOOBIG more than 2^32 - 16 of anything, or a bound on the output beyond that. */
+typedef struct vgk_read_alignments_policy {
+    uint32_t extension_score_threshold;   /* MinimizerMapper's field of that name (default 1) */
+    uint32_t max_local_extensions;        /* 0xffffffff: no limit */
+    uint32_t window_length;               /* k + w - 1, or k with syncmers */
+    uint32_t flags;                       /* 0 */
+} vgk_read_alignments_policy;
+enum { VGK_READ_ALN_DIRECT = 0, VGK_READ_ALN_BEST = 1, VGK_READ_ALN_SECOND = 2 };
+typedef struct vgk_read_alignment {      /* 56 B; the first 32 are a vgk_chain_result */
+    int32_t  status;
+    uint32_t mapping_begin, n_mappings;
+    uint32_t edit_begin, n_edits;
+    uint32_t from_length, to_length;
+    uint32_t read;                        /* the read it belongs to */
+    uint32_t kind;                        /* VGK_READ_ALN_* */
+    uint32_t extension;                   /* index into `extensions`; UINT32_MAX: none (an empty BEST / SECOND) */
+    int32_t  score;
+    uint32_t identity_num, identity_den;
+    uint32_t reserved;
+} vgk_read_alignment;
+int vgk_read_alignments(vgk_ctx* ctx, const vgk_haplo* index, const vgk_read_alignments_policy* policy,
+                        const char* reads, const uint64_t* read_off, uint32_t n, const vgk_gapless_result* results,
+                        const vgk_extension* extensions, size_t n_extensions, const uint32_t* nodes, size_t n_nodes, const uint32_t* mismatches, size_t n_mismatches,
+                        const vgk_tail_alignment* tails, size_t n_tails, const vgk_op* ops, size_t n_ops,
+                        uint64_t* aln_off /* [n + 1] */, vgk_read_alignment* alignments, size_t cap_alignments,
+                        vgk_chain_mapping* mappings, size_t cap_mappings, uint32_t* edits, size_t cap_edits, size_t written[3]);
+/* The resident form: vgk_tail_stage_aligned (vgk.h) followed by the same kernels over what lies in HBM — the sets the last vgk_gapless_extend(_seeded)
+ * call on this context left there, with their masked reads, and the tails' winning alignments and ops, which are made and consumed on the device: only
+ * ext_total, read_score (as vgk_tail_stage's) and the composed alignments cross PCIe.  The alignments are those vgk_read_alignments makes of the same
+ * call's downloaded sets and tails, byte for byte.  Outputs, capacities, VGK_EOPS and written[0..2] as vgk_read_alignments' (ext_total and read_score are
+ * complete on VGK_EOPS too: call again with the room named, after extending again); a VGK_GAPLESS_DEFER call's copies are finished when this call
+ * returns, as by the other two tail-stage entry points.  The sets are the engine's own: nothing is validated per read; a read whose extension failed
+ * has one header with that status. */
+int vgk_tail_stage_composed(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_per_problem, const vgk_read_alignments_policy* policy,
+                            int32_t* ext_total, size_t ext_cap, int32_t* read_score,
+                            uint64_t* aln_off /* [reads + 1] */, vgk_read_alignment* alignments, size_t cap_alignments,
+                            vgk_chain_mapping* mappings, size_t cap_mappings, uint32_t* edits, size_t cap_edits, size_t written[3], uint64_t stats[4]);
+/* out[0] = extensions of a set whose order and frontiers the selection keeps in LDS (a lane per read; larger sets run over a slab in HBM),
+ * out[1] = lanes per read in the selection, out[2] = lanes per read in count and emit, out[3] = 0 (reserved).  Needs no context. */
+int vgk_read_alignments_limits(uint32_t out[4]);
+/* Device time (ms) of the last vgk_read_alignments call on this context: selection | count + prefix sums | emit */
+int vgk_read_alignments_last_ms(vgk_ctx* ctx, double ms[3]);
+
 /* ---- windows of the resident graph, of any read length: the wide route on the device ------------------------------------------------------
  * vgk_gssw_pack_windows (vgk.h) takes what the packed kernels take: at most 1024 DP rows, scores inside 11 bits; a longer window fails the whole
  * pack with VGK_ETOOLONG.  This one-call entry takes windows of any read length and scoring and answers every problem in its own status, as

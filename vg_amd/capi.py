@@ -166,6 +166,51 @@ def extension_anchors_call(fn, head, match, mismatch, flags, max_mismatches, see
     return rc, out
 
 
+# vgk_read_alignments (include/vgk_engine.h): extension sets and their tails' alignments in, giraffe's alignments per read out
+READ_ALIGNMENT_DT = np.dtype([("status", "<i4"), ("mapping_begin", "<u4"), ("n_mappings", "<u4"), ("edit_begin", "<u4"), ("n_edits", "<u4"), ("from_length", "<u4"),
+                              ("to_length", "<u4"), ("read", "<u4"), ("kind", "<u4"), ("extension", "<u4"), ("score", "<i4"), ("identity_num", "<u4"),
+                              ("identity_den", "<u4"), ("reserved", "<u4")])
+assert READ_ALIGNMENT_DT.itemsize == 56
+READ_ALN_DIRECT, READ_ALN_BEST, READ_ALN_SECOND = 0, 1, 2
+READ_ALN_NO_EXTENSION = 0xffffffff
+
+
+class ReadAlignmentsPolicy(ctypes.Structure):   # vgk_read_alignments_policy
+    _fields_ = [("extension_score_threshold", ctypes.c_uint32), ("max_local_extensions", ctypes.c_uint32), ("window_length", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+def read_alignments_call(fn, head, reads, read_off, results, extensions, nodes, mismatches, tails=None, ops=None, extension_score_threshold=1,
+                         max_local_extensions=0xffffffff, window_length=39, caps=None, policy_flags=0, tail=()):
+    """one call with vgk_read_alignments' arguments (the engine's, the host shim's vgh_read_alignments, the serial lane code's): head / tail = the ctypes
+    values the function takes before `policy` / behind `written`.  caps = (alignments, mappings, edit runs): the room offered; None: sized by a first call with no room, as a C caller would
+    -> (rc, dict(aln_off, alignments READ_ALIGNMENT_DT, mappings CHAIN_MAPPING_DT, edits, written))"""
+    reads = np.ascontiguousarray(reads, dtype=np.uint8); off = np.ascontiguousarray(read_off, dtype=np.uint64); n = len(off) - 1
+    res = np.ascontiguousarray(results, dtype=GAPLESS_RESULT_DT); ext = np.ascontiguousarray(extensions, dtype=EXT_DT)
+    nod = np.ascontiguousarray(nodes, dtype=np.uint32); mis = np.ascontiguousarray(mismatches, dtype=np.uint32)
+    tl = np.zeros(0, dtype=TAIL_ALIGNMENT_DT) if tails is None else np.ascontiguousarray(tails, dtype=TAIL_ALIGNMENT_DT)
+    op = np.zeros(0, dtype=OP_DT) if ops is None else np.ascontiguousarray(ops, dtype=OP_DT)
+    policy = ReadAlignmentsPolicy(int(extension_score_threshold), int(max_local_extensions), int(window_length), int(policy_flags))
+    ptr = lambda a: a.ctypes.data if len(a) else None
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p] + [ctypes.c_void_p, ctypes.c_size_t] * 5 \
+        + [ctypes.c_void_p] + [ctypes.c_void_p, ctypes.c_size_t] * 3 + [ctypes.c_void_p] + [type(t) for t in tail]
+    written = (ctypes.c_size_t * 3)()
+    aln_off = np.zeros(n + 1, dtype=np.uint64)
+    rooms = [caps] if caps is not None else [(0, 0, 0), None]
+    for room in rooms:
+        cap = room if room is not None else tuple(int(x) for x in written)
+        aln = np.zeros(max(cap[0], 1), dtype=READ_ALIGNMENT_DT); maps = np.zeros(max(cap[1], 1), dtype=CHAIN_MAPPING_DT); edits = np.zeros(max(cap[2], 1), dtype=np.uint32)
+        rc = fn(*head, ctypes.byref(policy), ptr(reads), off.ctypes.data, n, ptr(res), ptr(ext), len(ext), ptr(nod), len(nod), ptr(mis), len(mis), ptr(tl), len(tl),
+                ptr(op), len(op), aln_off.ctypes.data, aln.ctypes.data, cap[0], maps.ctypes.data, cap[1], edits.ctypes.data, cap[2], written, *tail)
+        if rc != VGK_EOPS:
+            break
+    w = tuple(int(x) for x in written)
+    out = dict(aln_off=aln_off, alignments=aln, mappings=maps, edits=edits, written=w)
+    if rc == VGK_OK:
+        out.update(alignments=aln[:w[0]], mappings=maps[:w[1]], edits=edits[:w[2]])
+    return rc, out
+
+
 MINIMIZER_REVERSE = 1
 # vgk_chain_stitch (include/vgk.h): pieces of a read's chain in, one composed alignment per read out
 CHAIN_PIECE_DT = np.dtype([("kind", "<u4"), ("link", "<u4"), ("node_offset", "<u4"), ("path_begin", "<u4"), ("path_len", "<u4"), ("edit_begin", "<u4"), ("n_edits", "<u4"), ("reserved", "<u4")])
@@ -785,6 +830,54 @@ class Engine:
         ms = (ctypes.c_double * 3)()
         self.lib.vgk_extension_anchors_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._check(self.lib.vgk_extension_anchors_last_ms(self.h, ms), "vgk_extension_anchors_last_ms")
+        return tuple(float(x) for x in ms)
+
+    def read_alignments(self, index, reads, read_off, results, extensions, nodes, mismatches, tails=None, ops=None, extension_score_threshold=1,
+                        max_local_extensions=0xffffffff, window_length=39, caps=None):
+        """vgk_read_alignments (include/vgk_engine.h): per read the alignments giraffe makes of its extension set — one per leading full extension of a
+        full-length set, otherwise the best and the second best of find_optimal_tail_alignments — from the set (GAPLESS_RESULT_DT, EXT_DT with their nodes
+        and mismatches, as gapless_extend returns them) and the tails' alignments (TAIL_ALIGNMENT_DT, OP_DT, as tail_stage_aligned returns them).
+        window_length: k + w - 1 of the minimizer index (k with syncmers).  caps = (alignments, mappings, edit runs) offers that much room: VgkError on
+        VGK_EOPS.  -> dict(aln_off, alignments READ_ALIGNMENT_DT, mappings CHAIN_MAPPING_DT, edits, written)"""
+        rc, out = read_alignments_call(self.lib.vgk_read_alignments, (self.h, index.h), reads, read_off, results, extensions, nodes, mismatches,
+                                       tails, ops, extension_score_threshold, max_local_extensions, window_length, caps)
+        self.read_alignments_written = out["written"]
+        self._check(rc, "vgk_read_alignments")
+        return out
+
+    def tail_stage_composed(self, index, n_reads, n_ext, ops_per_problem=32, extension_score_threshold=1, max_local_extensions=0xffffffff, window_length=39, caps=None):
+        """vgk_tail_stage_composed (include/vgk_engine.h): the tail stage over the sets the last gapless_extend / gapless_extend_seeded call left on the device,
+        and the reads' alignments composed there from the tails' winners: neither tails nor ops come down.  caps = (alignments, mappings, edit runs): the
+        room offered; None: n_ext + 2 n_reads alignments (which always suffices) with 8 mappings and 12 edit runs each.  Too little room: VgkError
+        (VGK_EOPS) with self.read_alignments_written = what is needed — ext_total and read_score are complete by then; extend again and call with that room.
+        -> (ext_total, read_score, dict(aln_off, alignments READ_ALIGNMENT_DT, mappings CHAIN_MAPPING_DT, edits, written), stats)"""
+        ext_total = self._out("ts_ext", max(n_ext, 1), np.int32); read_score = self._out("ts_read", max(n_reads, 1), np.int32); stats = np.zeros(4, dtype=np.uint64)
+        cap = caps if caps is not None else (n_ext + 2 * n_reads + 1, 8 * (n_ext + 2 * n_reads) + 16, 12 * (n_ext + 2 * n_reads) + 16)
+        aln = self._out("tc_aln", max(cap[0], 1), READ_ALIGNMENT_DT); maps = self._out("tc_maps", max(cap[1], 1), CHAIN_MAPPING_DT); edits = self._out("tc_edits", max(cap[2], 1), np.uint32)
+        aln_off = np.zeros(n_reads + 1, dtype=np.uint64); written = (ctypes.c_size_t * 3)()
+        policy = ReadAlignmentsPolicy(int(extension_score_threshold), int(max_local_extensions), int(window_length), 0)
+        fn = self.lib.vgk_tail_stage_composed
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        rc = fn(self.h, index.h, ops_per_problem, ctypes.byref(policy), ext_total.ctypes.data, len(ext_total), read_score.ctypes.data, aln_off.ctypes.data,
+                aln.ctypes.data, cap[0], maps.ctypes.data, cap[1], edits.ctypes.data, cap[2], written, stats.ctypes.data)
+        w = tuple(int(x) for x in written)
+        self.read_alignments_written = w
+        self._check(rc, "vgk_tail_stage_composed")
+        return ext_total[:n_ext], read_score[:n_reads], dict(aln_off=aln_off, alignments=aln[:w[0]], mappings=maps[:w[1]], edits=edits[:w[2]], written=w), tuple(int(x) for x in stats)
+
+    def read_alignments_limits(self):
+        """-> (extensions of a set the selection keeps in LDS, lanes per read in the selection, lanes per read in count and emit, 0)"""
+        out = (ctypes.c_uint32 * 4)()
+        self._check(self.lib.vgk_read_alignments_limits(out), "vgk_read_alignments_limits")
+        return tuple(int(x) for x in out)
+
+    def read_alignments_last_ms(self):
+        """device time of the last read_alignments call: (selection, count + prefix sums, emit) in ms"""
+        ms = (ctypes.c_double * 3)()
+        self.lib.vgk_read_alignments_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_read_alignments_last_ms(self.h, ms), "vgk_read_alignments_last_ms")
         return tuple(float(x) for x in ms)
 
     def minimizer_last_ms(self):

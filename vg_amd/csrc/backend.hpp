@@ -24,6 +24,7 @@
 #include "chain_device.hpp"
 #include "chain_items_device.hpp"
 #include "extension_anchors_device.hpp"
+#include "read_alignments_device.hpp"
 
 namespace vgk {
 
@@ -168,6 +169,9 @@ public:
     // extension (COUNT, EMIT), or `blocks` wavefronts over the problems p.ids[0 .. p.n) (SORT, ANCHORS): a problem each in LDS, or (p.slab) striding over
     // them with a slab each.  Optional
     virtual int   run_extension_anchors(const EaParams& p, int what, uint32_t blocks) { (void)p; (void)what; (void)blocks; return VGK_EUNSUPPORTED; }
+    // one stage of vgk_read_alignments (read_alignments_device.hpp: RA_RUN_*), asynchronous on the main stream: a lane per read — the selection over the
+    // reads p.ids[0 .. p.n), their working words in LDS or (p.work) in the slab; count and emit over all p.n_reads.  Optional
+    virtual int   run_read_alignments(const RaParams& p, int what) { (void)p; (void)what; return VGK_EUNSUPPORTED; }
     virtual int   run_tail(const TailParams& p, uint32_t threads) = 0;
     virtual int   run_tail_stage(const TStageParams& p, int what) = 0;     // one of the per-item stages of vgk_tail_stage (tail_device.hpp: TS_*)
     virtual int   run_rescue_requests(const RqParams& p, int what) = 0;    // one of the per-pair stages of vgk_rescue_requests (rescue_requests_device.hpp: RQ_*)

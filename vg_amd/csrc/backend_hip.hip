@@ -1264,6 +1264,27 @@ __global__ void __launch_bounds__(64) extension_anchors_slab_kernel(const EaPara
     for (uint32_t i = blockIdx.x; i < P.n; i += gridDim.x) { ea_anchors_problem(P, P.ids[i], order, order + P.slab_np, threadIdx.x); __syncthreads(); }
 }
 // ---- one Path per read (chain_device.hpp): a lane per read for the bounds and the composition, a wavefront per read for the dense copy
+// ---- a short read's alignments from its extension set and its tails (read_alignments_device.hpp: ra_read_one is the rule and the checker).  A lane per
+// read.  The selection's working words lie in LDS, one slice per lane at an odd stride (no two lanes of a wavefront in one bank), for sets of up to
+// RA_LDS_EXT extensions; the reads with larger sets come in a launch of their own over slices of a slab in HBM.  Count and emit are the one composer.
+__global__ void __launch_bounds__(64) read_alignments_select_kernel(const RaParams P) {
+    __shared__ uint32_t work[64 * RA_LDS_STRIDE];
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= P.n) return;
+    const uint32_t r = P.ids ? P.ids[i] : i;
+    // (the resident form: every read in one launch; the few large sets take their slices of the slab, by the extensions before them)
+    uint32_t* mine = work + threadIdx.x * RA_LDS_STRIDE;
+    if (P.work && P.res[r].n_ext > RA_LDS_EXT) mine = P.work + 9ull * P.res[r].ext_begin + 4ull * r;
+    ra_read_one(P, RA_RUN_SELECT, r, mine);
+}
+__global__ void __launch_bounds__(64) read_alignments_select_slab_kernel(const RaParams P) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < P.n) ra_read_one(P, RA_RUN_SELECT, P.ids[i], P.work + P.work_off[i]);
+}
+__global__ void __launch_bounds__(64) read_alignments_compose_kernel(const RaParams P, const int what) {
+    const uint32_t r = blockIdx.x * 64 + threadIdx.x;
+    if (r < (what == RA_RUN_TAILS ? P.n_tails : P.n_reads)) ra_read_one(P, what, r, nullptr);
+}
 __global__ void __launch_bounds__(64) chain_stitch_kernel(const CsParams P, const int what) {
     cs_one(P, what, blockIdx.x * 64 + threadIdx.x);
 }
@@ -2125,6 +2146,19 @@ public:
                 if (p.slab) hipLaunchKernelGGL(extension_anchors_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
                 else hipLaunchKernelGGL(extension_anchors_kernel, dim3(blocks), dim3(64), lds, stream, p);
             }
+        } else return VGK_EINVAL;
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_read_alignments(const RaParams& p, int what) override {
+        hipSetDevice(dev);
+        if (what == RA_RUN_SELECT) {
+            if (!p.n) return VGK_OK;
+            if (p.work && p.ids) hipLaunchKernelGGL(read_alignments_select_slab_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
+            else hipLaunchKernelGGL(read_alignments_select_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
+        } else if (what == RA_RUN_COUNT || what == RA_RUN_EMIT || what == RA_RUN_TAILS) {
+            const uint32_t items = what == RA_RUN_TAILS ? p.n_tails : p.n_reads;
+            if (!items) return VGK_OK;
+            hipLaunchKernelGGL(read_alignments_compose_kernel, dim3((items + 63) / 64), dim3(64), 0, stream, p, what);
         } else return VGK_EINVAL;
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }

@@ -95,7 +95,7 @@ struct vgk_ctx {
     // vgk_tail_stage derives the tails from there
     struct Sets { bool valid = false; uint32_t n = 0; uint64_t n_ext = 0; const void* probs = nullptr; const char* reads = nullptr;
                   const void* res = nullptr; const void* ext = nullptr; const uint32_t* nodes = nullptr; const void* index = nullptr;
-                  const uint32_t* read_of = nullptr; } sets;      // read_of[e]: the read extension e belongs to
+                  const uint32_t* read_of = nullptr; const uint32_t* mism = nullptr; } sets;      // read_of[e]: the read extension e belongs to
     // VGK_GAPLESS_DEFER: the sets of that call are still on their way down (fetch stream -> page-locked staging) and have yet to be
     // copied into the caller's arrays; finished by vgk_tail_stage*, vgk_gapless_fetch_deferred, or the next extension call
     struct DeferredSpan { char* dst; const char* src; size_t bytes; };
@@ -106,6 +106,7 @@ struct vgk_ctx {
     double minimizer_choose_ms = 0; // ... and of the choice kernels of the last vgk_minimizer_choose / vgk_minimizer_find_seeds call
     double chain_items_ms[3] = {0, 0, 0};   // last vgk_chain_items: legality + grouping | DP | traceback
     double extension_anchors_ms[3] = {0, 0, 0};   // last vgk_extension_anchors: seed anchors + diagonal sort | the extensions' seed lists | anchors
+    double read_alignments_ms[3] = {0, 0, 0};   // last vgk_read_alignments: selection | count + prefix sums | emit
     double tail_stage_ms[4] = {0, 0, 0, 0};   // last vgk_tail_stage: tails derived | forest | windows packed | kernels + totals
     double tail_ms = 0;            // device time of the last vgk_tail_forest call
     // the last batch of either call stays resident in the cached device buffers: what a re-run needs to launch it again

@@ -404,7 +404,7 @@ static int gapless_run_and_fetch(vgk_ctx* ctx, GaplessParams& P, uint32_t n, uin
     for (int k = 0; k < 3; ++k) if ((rc = be->download(&tot[k], tab + (3 + k) * n1 + n, sizeof(uint32_t)))) return cleanup(rc);
     const size_t we = tot[0], wn = tot[1], wm = tot[2];
     ctx->sets.valid = true; ctx->sets.n = n; ctx->sets.n_ext = tot[0]; ctx->sets.probs = P.probs; ctx->sets.reads = P.reads;
-    ctx->sets.res = O.res_out; ctx->sets.ext = O.ext_out; ctx->sets.nodes = O.nodes_out; ctx->sets.index = nullptr; ctx->sets.read_of = O.read_of;
+    ctx->sets.res = O.res_out; ctx->sets.ext = O.ext_out; ctx->sets.nodes = O.nodes_out; ctx->sets.index = nullptr; ctx->sets.read_of = O.read_of; ctx->sets.mism = O.mism_out;
     int rc_all = VGK_OK;
     vgk_gapless_result* dres = H.dres.get(be, n);
     vgk_extension* dext = H.dext.get(be, we + 1); uint32_t* dnodes = H.dnodes.get(be, wn + 1); uint32_t* dmism = H.dmism.get(be, wm + 1);

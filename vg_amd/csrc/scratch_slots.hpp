@@ -52,6 +52,12 @@ enum Slot : int {
     // the prefix sums, the lists; the error flag; the anchors as made and sorted with their origins, the represented seeds, the per-problem counts; the slabs
     EANCH_PROBS, EANCH_SEEDS, EANCH_EXT, EANCH_NODES, EANCH_MISM, EANCH_PROB_OF_EXT, EANCH_IDS, EANCH_SEED_ANCHOR, EANCH_SORTED, EANCH_EXT_COUNT, EANCH_EXT_FIRST,
     EANCH_EXT_SEEDS, EANCH_FLAGS, EANCH_MADE, EANCH_MADE_ORIGIN, EANCH_ANCHORS, EANCH_ORIGINS, EANCH_REP, EANCH_N_ANCHORS, EANCH_N_REP, EANCH_STATUS, EANCH_SLAB,
+    // ---- read_alignments_api.cpp (nothing stays): the reads and their inputs (offsets, gapless results, extensions, path nodes, mismatches, tails, ops, the
+    // tails of each extension, the validation's verdicts), the launches' reads and the large sets' slab; per read the choice and the alignments it has,
+    // their prefix sums; per alignment the mappings and edit runs it has, their prefix sums and 64-bit totals; the headers, mappings and edit runs
+    READALN_READS, READALN_READ_OFF, READALN_RES, READALN_EXT, READALN_NODES, READALN_MISM, READALN_TAILS, READALN_OPS, READALN_TAIL_OF, READALN_STATUS,
+    READALN_IDS, READALN_WORK_OFF, READALN_WORK, READALN_CHOICE, READALN_ALN_COUNT, READALN_ALN_FIRST, READALN_MAP_COUNT, READALN_EDIT_COUNT,
+    READALN_MAP_FIRST, READALN_EDIT_FIRST, READALN_OUT, READALN_MAPPINGS, READALN_EDITS, READALN_TOTALS,
     // ---- gssw_wide_window_api.cpp (nothing stays): the call's problems, reads and verdicts; a sub-batch's windows, per-node temporaries, sizes, their
     // sums, the order's keys; the results and ops packed for the way back.  The arenas the wide kernels read are the WIDE_* buffers (aliases below)
     WIDEWIN_PROBLEMS, WIDEWIN_READS, WIDEWIN_META, WIDEWIN_SUB, WIDEWIN_STORE, WIDEWIN_NODE_FLAGS, WIDEWIN_SLOT_AT, WIDEWIN_PRED_AT, WIDEWIN_WIN_SLOTS,

@@ -4,6 +4,7 @@
 // The host's share is the problem array up (20 B per tail) and the result array down (24 B per tail) plus two 4-byte totals that
 // size the device allocations; the trees, their bases and the packer's tables never leave HBM (vgk_forest_fetch copies the
 // (parent, node, length) triples out for the caller that wants to translate alignments back — TreeSubgraph::translate_down).
+#include <cstddef>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +14,7 @@
 #include <new>
 #include <vector>
 #include "ctx.hpp"
+#include "../../include/vgk_engine.h"
 #include "dgraph.hpp"
 #include "haplo.hpp"
 #include "batch.hpp"
@@ -150,9 +152,18 @@ int vgk_pack_windows_impl(vgk_ctx* ctx, const vgk_dgraph* dg, const char* reads,
                           const vgk_window_problem* problems, uint32_t n, uint32_t ops_per_problem, vgk_batch** out, bool on_device, uint32_t forced_k,
                           const vgk::WinExt* extensions);
 }  // extern "C"
-// aligned / tails_cap / ops / ops_cap / written: vgk_tail_stage_aligned's outputs (all null / 0 for vgk_tail_stage)
+int vgk_read_alignments_run(vgk_ctx* ctx, vgk::RaParams& P, const uint32_t* d_ids, uint32_t n_lds, uint32_t n_large, uint32_t* d_work, const uint64_t* d_work_off, uint64_t out_bound,
+                            uint64_t* aln_off, vgk_read_alignment* alignments, size_t cap_alignments, vgk_chain_mapping* mappings, size_t cap_mappings,
+                            uint32_t* edits, size_t cap_edits, size_t written[3]);      // read_alignments_api.cpp
+static_assert(offsetof(vgk::GProb, read_off) == 0 && offsetof(vgk::GProb, read_len) == 4 && sizeof(vgk::GProb) % 4 == 0, "RaParams::prob_words reads a GProb's first two words");
+// vgk_tail_stage_composed's policy and outputs: the third mode of tail_stage_impl
+struct TailComposed { const vgk_read_alignments_policy* policy; uint64_t* aln_off; vgk_read_alignment* alignments; size_t cap_alignments; vgk_chain_mapping* mappings; size_t cap_mappings;
+                      uint32_t* edits; size_t cap_edits; size_t* written; };
+// aligned / tails_cap / ops / ops_cap / written: vgk_tail_stage_aligned's outputs (all null / 0 for vgk_tail_stage).  composed: the winners' ops stay in
+// HBM (nothing of `aligned` / `ops` is read or written) and the alignments are composed from them there (read_alignments_device.hpp)
 static int tail_stage_impl(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_per_problem, int32_t* ext_total, size_t ext_cap, int32_t* read_score, uint64_t stats[4],
-                           const bool want_aligned, vgk_tail_alignment* aligned, size_t tails_cap, vgk_op* ops, size_t ops_cap, size_t* written) {
+                           const bool want_aligned, vgk_tail_alignment* aligned, size_t tails_cap, vgk_op* ops, size_t ops_cap, size_t* written,
+                           const TailComposed* composed = nullptr) {
     if (!ctx || !index || !vgk_tables_usable(index->ctx, ctx)) return VGK_EINVAL;
     if (written) written[0] = written[1] = 0;
     if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
@@ -160,6 +171,8 @@ static int tail_stage_impl(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_pe
     std::lock_guard<std::mutex> stage(ctx->stage_mu);                     // the sets, the resident reads and the scratch slots they live in stay this call's while mu is let go below
     std::unique_lock<std::mutex> lk(ctx->mu);
     if (!ctx->sets.valid) return VGK_EINVAL;
+    if (composed && (!composed->policy || composed->policy->flags || !composed->policy->window_length || !composed->aln_off || !ctx->sets.mism)) return VGK_EINVAL;
+    if (composed && ctx->has_qa) return VGK_EUNSUPPORTED;
     const uint32_t n = ctx->sets.n; const uint64_t n_ext = ctx->sets.n_ext;
     if (n_ext > ext_cap || (n_ext && !ext_total) || (n && !read_score) || n_ext > 0xfffffff0ull) return VGK_EINVAL;
     std::vector<vgk_ctx::Pooled> temp;                                     // device blocks of this call: back to the pool at the end
@@ -192,7 +205,8 @@ static int tail_stage_impl(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_pe
     const uint32_t nt = tot_rl[0] + tot_rl[1];
     S.total_r = tot_rl[0]; S.n_tails = nt;
     wall("counted");
-    uint64_t n_trees = 0, tree_nodes = 0;
+    uint64_t n_trees = 0, tree_nodes = 0, n_tail_ops = 0;
+    const vgk_tail_alignment* d_aligned = nullptr; const vgk_op* d_out_ops = nullptr;      // what the composition reads: alive until done()
     unsigned long long failed = 0;
     if (nt) {
         const size_t t1 = (size_t)nt + 1;
@@ -206,7 +220,7 @@ static int tail_stage_impl(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_pe
         uint32_t* d_ops_tab = nullptr;
         if (want_aligned) {
             if (written) written[0] = nt;
-            if (nt > tails_cap || !aligned) return done(VGK_EOPS);
+            if (!composed && (nt > tails_cap || !aligned)) return done(VGK_EOPS);
             S.tail_best = (unsigned long long*)take(sizeof(unsigned long long) * t1);
             d_ops_tab = (uint32_t*)take(sizeof(uint32_t) * 2 * t1);
             S.aligned = (vgk_tail_alignment*)take(sizeof(vgk_tail_alignment) * t1);
@@ -254,12 +268,13 @@ static int tail_stage_impl(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_pe
             if (!r2) r2 = be->download(&n_ops, S.ops_off + nt, sizeof(uint32_t));
             if (r2) return r2;
             if (written) written[1] = n_ops;
-            if (n_ops > ops_cap || (n_ops && !ops)) return VGK_EOPS;
+            n_tail_ops = n_ops;
+            if (!composed && (n_ops > ops_cap || (n_ops && !ops))) return VGK_EOPS;
             S.out_ops = (vgk_op*)take(sizeof(vgk_op) * ((size_t)n_ops + 1));
             if (!S.out_ops) return VGK_ENOMEM;
             r2 = be->run_tail_stage(S, TS_OPS_COPY);
-            if (!r2) r2 = be->download(aligned, S.aligned, sizeof(vgk_tail_alignment) * nt);
-            if (!r2 && n_ops) r2 = be->download(ops, S.out_ops, sizeof(vgk_op) * n_ops);
+            if (!r2 && !composed) r2 = be->download(aligned, S.aligned, sizeof(vgk_tail_alignment) * nt);
+            if (!r2 && n_ops && !composed) r2 = be->download(ops, S.out_ops, sizeof(vgk_op) * n_ops);
             return r2;
         };
         if (nw) {
@@ -291,6 +306,7 @@ static int tail_stage_impl(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_pe
             rc = winners_down(nullptr);
             if (rc) { drop_forest(); return done(rc); }
         }
+        d_aligned = S.aligned; d_out_ops = S.out_ops;
         rc = be->run_tail_stage(S, TS_TOTAL);
         if (!rc) rc = be->sync();
         drop_forest();
@@ -302,6 +318,30 @@ static int tail_stage_impl(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_pe
     if (!rc) rc = be->download(&failed, d_failed, sizeof failed);
     be->watch(1); be->sync(); ctx->tail_stage_ms[3] = be->watch_ms();
     if (stats) { stats[0] = nt; stats[1] = n_trees; stats[2] = tree_nodes; stats[3] = failed; }
+    if (!rc && composed) {
+        // the alignments, from what lies in HBM: the sets in problem order with their masked reads (a masked base never matches, as a base that is
+        // not ACGT never does), the tails' winners and their ops; the table of each extension's tails is made there too
+        composed->aln_off[0] = 0;
+        if (composed->written) composed->written[0] = composed->written[1] = composed->written[2] = 0;
+        if (n && (n_ext + 2ull * n > 0xfffffff0ull || n_tail_ops > 0xfffffff0ull)) rc = VGK_ETOOBIG;
+        if (!rc && n) {
+            RaParams R{};
+            R.match = ctx->sc.matrix[0]; R.mismatch = -ctx->sc.matrix[1]; R.gap_open = ctx->sc.gap_open; R.gap_extend = ctx->sc.gap_extend; R.bonus = ctx->sc.full_length_bonus;
+            R.threshold = composed->policy->extension_score_threshold; R.max_local = composed->policy->max_local_extensions; R.window_length = composed->policy->window_length;
+            R.n_reads = n; R.n_oriented = index->n_oriented; R.node_tab = index->dev.node_tab; R.seq = index->dev.seq;
+            R.reads = ctx->sets.reads; R.prob_words = (const uint32_t*)ctx->sets.probs; R.prob_stride = (uint32_t)(sizeof(GProb) / 4);
+            R.res = (const vgk_gapless_result*)ctx->sets.res; R.ext = (const vgk_extension*)ctx->sets.ext; R.nodes = ctx->sets.nodes; R.mism = ctx->sets.mism;
+            R.tails = d_aligned; R.ops = d_out_ops; R.n_tails = nt;
+            R.tail_of_out = (uint32_t*)ctx->ensure_scratch(READALN_TAIL_OF, sizeof(uint32_t) * 2 * (n_ext + 1));
+            uint32_t* d_work = (uint32_t*)ctx->ensure_scratch(READALN_WORK, sizeof(uint32_t) * (9 * n_ext + 4ull * n + 4));
+            R.tail_of = R.tail_of_out;
+            if (!R.tail_of_out || !d_work) rc = VGK_ENOMEM;
+            if (!rc) rc = be->fill(R.tail_of_out, 0xff, sizeof(uint32_t) * 2 * (n_ext + 1));
+            if (!rc && nt) rc = be->run_read_alignments(R, RA_RUN_TAILS);
+            if (!rc) rc = vgk_read_alignments_run(ctx, R, nullptr, 0, 0, d_work, nullptr, 0xfffffff0ull, composed->aln_off, composed->alignments, composed->cap_alignments,
+                                                  composed->mappings, composed->cap_mappings, composed->edits, composed->cap_edits, composed->written);
+        }
+    }
     wall("totals down");
     rc = done(rc);
     wall("blocks back to the pool");
@@ -316,6 +356,14 @@ int vgk_tail_stage(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_per_proble
 int vgk_tail_stage_aligned(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_per_problem, int32_t* ext_total, size_t ext_cap, int32_t* read_score,
                            vgk_tail_alignment* tails, size_t tails_cap, vgk_op* ops, size_t ops_cap, size_t written[2], uint64_t stats[4]) try {
     int rc = tail_stage_impl(ctx, index, ops_per_problem, ext_total, ext_cap, read_score, stats, true, tails, tails_cap, ops, ops_cap, written);
+    if (ctx) { std::lock_guard<std::mutex> lk(ctx->mu); const int rc2 = ctx->finish_deferred(); if (!rc) rc = rc2; }
+    return rc;
+} catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }      // (no exception leaves the C ABI)
+int vgk_tail_stage_composed(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_per_problem, const vgk_read_alignments_policy* policy, int32_t* ext_total, size_t ext_cap, int32_t* read_score,
+                            uint64_t* aln_off, vgk_read_alignment* alignments, size_t cap_alignments, vgk_chain_mapping* mappings, size_t cap_mappings,
+                            uint32_t* edits, size_t cap_edits, size_t written[3], uint64_t stats[4]) try {
+    const TailComposed c{policy, aln_off, alignments, cap_alignments, mappings, cap_mappings, edits, cap_edits, written};
+    int rc = tail_stage_impl(ctx, index, ops_per_problem, ext_total, ext_cap, read_score, stats, true, nullptr, 0, nullptr, 0, nullptr, &c);
     if (ctx) { std::lock_guard<std::mutex> lk(ctx->mu); const int rc2 = ctx->finish_deferred(); if (!rc) rc = rc2; }
     return rc;
 } catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }      // (no exception leaves the C ABI)

@@ -21,6 +21,7 @@
 #include "rescue_stage.hpp"
 #include "rescue_resident.hpp"
 #include "rescue_requests.hpp"
+#include "read_alignments.hpp"
 #include <sstream>
 
 using namespace vgamd;
@@ -1184,6 +1185,135 @@ int64_t vgh_find_anchor_intervals(uint64_t read_begin, uint64_t read_end, const 
         for (size_t k = 0; k < found.size() && k < cap; ++k) { intervals[2 * k] = found[k].first; intervals[2 * k + 1] = found[k].second; }
         return (int64_t)found.size();
     } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+// read_alignments (read_alignments.hpp) for a batch of reads, over the flat arrays of the engine's vgk_read_alignments (include/vgk_engine.h) and with its
+// output layout; scores = match, mismatch, gap open, gap extend, full-length bonus; oriented_node_length / oriented_seq (the oriented nodes' bases behind
+// each other) stand for the index.  A read whose input is malformed has one header with VGK_EINVAL, as the engine's; a malformed call answers VGK_EINVAL.
+// The per-read checks are written out here in the shim's own words — the list is that of include/vgk_engine.h, the engine's is ra_validate_read — and
+// tests/test_read_alignments.py holds the two to each other case by case.
+// Reads on `threads` host threads (0 = all).
+int vgh_read_alignments(const int32_t scores[5], const uint32_t* oriented_node_length, const char* oriented_seq, uint64_t n_oriented,
+                        const vgk_read_alignments_policy* policy, const char* reads, const uint64_t* read_off, uint32_t n, const vgk_gapless_result* results,
+                        const vgk_extension* extensions, size_t n_extensions, const uint32_t* nodes, size_t n_nodes, const uint32_t* mismatches, size_t n_mismatches,
+                        const vgk_tail_alignment* tails, size_t n_tails, const vgk_op* ops, size_t n_ops,
+                        uint64_t* aln_off, vgk_read_alignment* alignments, size_t cap_alignments,
+                        vgk_chain_mapping* mappings, size_t cap_mappings, uint32_t* edits, size_t cap_edits, size_t written[3], int threads) {
+    try {
+        if (!policy || policy->flags || !policy->window_length) return VGK_EINVAL;
+        aln_off[0] = 0;
+        if (written) written[0] = written[1] = written[2] = 0;
+        if (!n) return 0;
+        if (read_off[0] != 0) return VGK_EINVAL;
+        for (uint32_t r = 0; r < n; ++r) if (read_off[r + 1] < read_off[r]) return VGK_EINVAL;
+        std::vector<uint64_t> seq_off(n_oriented + 1, 0);
+        for (uint64_t o = 0; o < n_oriented; ++o) seq_off[o + 1] = seq_off[o] + oriented_node_length[o];
+        const OrientedGraph graph{oriented_node_length, seq_off.data(), oriented_seq};
+        const TailScores scorer{scores[0], scores[1], scores[2], scores[3], scores[4]};
+        // which tail belongs to which end: -1 none, -2 claimed twice
+        std::vector<int64_t> tail_at(2 * n_extensions + 2, -1);
+        for (size_t t = 0; t < n_tails; ++t) {
+            if (tails[t].ext >= n_extensions || tails[t].left > 1) return VGK_EINVAL;
+            int64_t& slot = tail_at[2 * (size_t)tails[t].ext + tails[t].left];
+            slot = slot == -1 ? (int64_t)t : -2;
+        }
+        std::vector<std::vector<ReadAlignment>> made(n); std::vector<int32_t> status(n, 0);
+        unsigned T = threads > 0 ? (unsigned)threads : std::max(1u, std::thread::hardware_concurrency());
+        T = std::min<unsigned>(T, std::max<uint32_t>(1, n / 64));
+        std::atomic<uint32_t> next{0}; std::atomic<bool> failed{false}; std::string what; std::mutex what_mu;
+        auto load_tail = [&](int64_t at, bool left, const SetExtension& x, size_t seq_len, TailResult& out) -> bool {
+            if (at == -1) return true;
+            if (at == -2 || (left ? x.left_full : x.right_full)) return false;
+            const vgk_tail_alignment& t = tails[at];
+            if (t.read_begin != (left ? 0u : x.read_interval.second) || t.read_end != (left ? x.read_interval.first : seq_len) || (uint64_t)t.ops_begin + t.n_ops > n_ops) return false;
+            uint64_t spent_read = 0, on_node = t.first_offset;
+            for (uint32_t k = 0; k < t.n_ops; ++k) {
+                const vgk_op& o = ops[t.ops_begin + k];
+                if (!o.len || o.op > 3 || o.node >= n_oriented) return false;
+                const bool on_graph = o.op == 0 || o.op == 2;
+                if (k && (o.node != ops[t.ops_begin + k - 1].node || (on_graph && on_node >= oriented_node_length[o.node]))) on_node = 0;
+                if (on_graph) on_node += o.len;
+                if (o.op != 2) spent_read += o.len;
+                if (on_node > oriented_node_length[o.node]) return false;
+                out.ops.push_back(TailOp{o.node, o.len, o.op});
+            }
+            if (spent_read > (uint64_t)t.read_end - t.read_begin) return false;
+            out.score = t.n_ops ? t.score : 0; out.first_offset = t.first_offset;
+            return true;
+        };
+        auto work = [&]() {
+            try {
+                for (uint32_t r = next.fetch_add(1); r < n; r = next.fetch_add(1)) {
+                    const vgk_gapless_result g = results[r];
+                    made[r].clear();
+                    if (g.status != VGK_OK) { status[r] = g.status; continue; }
+                    const std::string sequence(reads + read_off[r], reads + read_off[r + 1]);
+                    bool ok = (uint64_t)g.ext_begin + g.n_ext <= n_extensions;
+                    std::vector<SetExtension> set;
+                    for (uint32_t k = 0; ok && k < g.n_ext; ++k) {
+                        const vgk_extension& y = extensions[g.ext_begin + k];
+                        if (!y.path_len || (uint64_t)y.path_begin + y.path_len > n_nodes || (uint64_t)y.mism_begin + y.n_mismatches > n_mismatches || y.read_begin >= y.read_end
+                            || y.read_end > sequence.size()) { ok = false; break; }
+                        SetExtension x; x.path.assign(nodes + y.path_begin, nodes + y.path_begin + y.path_len); x.offset = y.offset; x.read_interval = {y.read_begin, y.read_end};
+                        x.mismatch_positions.assign(mismatches + y.mism_begin, mismatches + y.mism_begin + y.n_mismatches); x.left_full = y.left_full != 0; x.right_full = y.right_full != 0;
+                        x.score = y.score;
+                        uint64_t before_last = 0;
+                        for (size_t i = 0; i < x.path.size(); ++i) { if (x.path[i] >= n_oriented) { ok = false; break; } if (i + 1 < x.path.size()) before_last += oriented_node_length[x.path[i]]; }
+                        if (!ok) break;
+                        const uint64_t span = x.offset + (uint64_t)(y.read_end - y.read_begin);
+                        if (x.offset >= oriented_node_length[x.path.front()] || span <= before_last || span - before_last > oriented_node_length[x.path.back()]) { ok = false; break; }
+                        for (size_t i = 0; i < x.mismatch_positions.size(); ++i)
+                            if (x.mismatch_positions[i] < y.read_begin || x.mismatch_positions[i] >= y.read_end || (i && x.mismatch_positions[i] <= x.mismatch_positions[i - 1])) ok = false;
+                        if (x.left_full != (y.read_begin == 0) || x.right_full != (y.read_end == sequence.size())) ok = false;
+                        if (ok) ok = load_tail(tail_at[2 * ((size_t)g.ext_begin + k)], false, x, sequence.size(), x.right_tail) && load_tail(tail_at[2 * ((size_t)g.ext_begin + k) + 1], true, x, sequence.size(), x.left_tail);
+                        set.push_back(std::move(x));
+                    }
+                    if (ok && g.full_length && (set.empty() || !set.front().full())) ok = false;
+                    if (!ok) { status[r] = VGK_EINVAL; continue; }
+                    made[r] = read_alignments(sequence, set, g.full_length != 0, graph, scorer, (int)policy->extension_score_threshold,
+                                              policy->max_local_extensions == 0xffffffffu ? SIZE_MAX : (size_t)policy->max_local_extensions, policy->window_length);
+                }
+            } catch (std::exception& e) { failed = true; std::lock_guard<std::mutex> lk(what_mu); what = e.what(); }
+        };
+        std::vector<std::thread> pool;
+        for (unsigned t = 1; t < T; ++t) pool.emplace_back(work);
+        work();
+        for (std::thread& t : pool) t.join();
+        if (failed) { g_last_error = what; return VGK_EINVAL; }
+        uint64_t n_aln = 0, n_maps = 0, n_edits = 0;
+        for (uint32_t r = 0; r < n; ++r) {
+            if (status[r] != VGK_OK) { ++n_aln; continue; }
+            for (const ReadAlignment& a : made[r]) { ++n_aln; n_maps += a.alignment.path.mapping.size(); for (const Mapping& m : a.alignment.path.mapping) n_edits += m.edit.size(); }
+        }
+        if (written) { written[0] = n_aln; written[1] = n_maps; written[2] = n_edits; }
+        if (n_aln > cap_alignments || n_maps > cap_mappings || n_edits > cap_edits) return VGK_EOPS;
+        uint64_t at = 0, map_at = 0, edit_at = 0;
+        for (uint32_t r = 0; r < n; ++r) {
+            aln_off[r] = at;
+            if (status[r] != VGK_OK) {
+                vgk_read_alignment h{}; h.status = status[r]; h.mapping_begin = (uint32_t)map_at; h.edit_begin = (uint32_t)edit_at; h.read = r; h.extension = 0xffffffffu;
+                alignments[at++] = h; continue;
+            }
+            for (const ReadAlignment& a : made[r]) {
+                vgk_read_alignment h{};
+                h.mapping_begin = (uint32_t)map_at; h.edit_begin = (uint32_t)edit_at; h.read = r; h.kind = (uint32_t)a.kind;
+                h.extension = a.extension == SIZE_MAX ? 0xffffffffu : (uint32_t)(results[r].ext_begin + a.extension); h.score = a.alignment.score;
+                h.identity_num = a.identity_num; h.identity_den = a.identity_den;
+                for (const Mapping& m : a.alignment.path.mapping) {
+                    vgk_chain_mapping out{(uint32_t)((m.position.node_id - 1) * 2 + (m.position.is_reverse ? 1 : 0)), (uint32_t)m.position.offset, (uint32_t)edit_at, (uint32_t)m.edit.size()};
+                    for (const Edit& e : m.edit) {
+                        const uint32_t kind = edit_is_match(e) ? VGK_WFA_MATCH : edit_is_sub(e) ? VGK_WFA_MISMATCH : edit_is_insertion(e) ? VGK_WFA_INSERTION : VGK_WFA_DELETION;
+                        edits[edit_at++] = (uint32_t)std::max(e.from_length, e.to_length) << 2 | kind;
+                        h.from_length += (uint32_t)e.from_length; h.to_length += (uint32_t)e.to_length;
+                    }
+                    mappings[map_at++] = out;
+                }
+                h.n_mappings = (uint32_t)a.alignment.path.mapping.size(); h.n_edits = (uint32_t)(edit_at - h.edit_begin);
+                alignments[at++] = h;
+            }
+        }
+        aln_off[n] = at;
+        return 0;
+    } catch (std::exception& e) { g_last_error = e.what(); return VGK_EINVAL; }
 }
 // extension_anchors (extension_anchors.hpp) for a batch of problems, over the flat arrays of the engine's vgk_extension_anchors (include/vgk_engine.h)
 // and with its output layout; oriented_node_length[n_oriented] stands for the index.  Nothing is validated beyond what keeps the arrays' bounds: a

@@ -264,10 +264,12 @@ def chain_stage(eng, index, wl, match=1, timing=None):
     return out
 
 
-def align_stage_device(eng, index, gs, ops_per_problem=32, timing=None, seeded=None, aligned=False):
+def align_stage_device(eng, index, gs, ops_per_problem=32, timing=None, seeded=None, aligned=False, composed=False, composed_policy=None, composed_caps=None):
     """The stage with everything behind the extension on the device too (vgk_tail_stage): the extension sets come back for the caller, the
     tails are derived, walked, packed and aligned from what the extension call left in HBM.  -> dict(res, ext, nodes, ext_total, read_score, stats); aligned:
-    also the tails' winning alignments (vgk_tail_stage_aligned: `tails`, `tail_ops`)"""
+    also the tails' winning alignments (vgk_tail_stage_aligned: `tails`, `tail_ops`); composed: instead the reads' alignments, made on the device from the
+    tails' winners without those coming down (vgk_tail_stage_composed: `composed` = dict(aln_off, alignments, mappings, edits, written); composed_policy:
+    extension_score_threshold / max_local_extensions / window_length).  `mism`: the extension call's mismatch positions, beside `nodes`"""
     import time
     t0 = time.perf_counter()
     if seeded is not None:
@@ -276,8 +278,10 @@ def align_stage_device(eng, index, gs, ops_per_problem=32, timing=None, seeded=N
     else:
         res, ext, nodes, mism = eng.gapless_extend(index, gs, defer=True)
     t1 = time.perf_counter()
-    tails = tail_ops = None
-    if aligned:
+    tails = tail_ops = made = None
+    if composed:
+        ext_total, read_score, made, stats = eng.tail_stage_composed(index, gs.n, len(ext), ops_per_problem, caps=composed_caps, **(composed_policy or {}))
+    elif aligned:
         ext_total, read_score, tails, tail_ops, stats = eng.tail_stage_aligned(index, gs.n, len(ext), ops_per_problem)
     else:
         ext_total, read_score, stats = eng.tail_stage(index, gs.n, len(ext), ops_per_problem)
@@ -287,7 +291,28 @@ def align_stage_device(eng, index, gs, ops_per_problem=32, timing=None, seeded=N
             timing[k] = timing.get(k, 0.0) + v
         for k, v in zip(("tails derived (device)", "tail forest (device)", "windows packed (device)", "fill + traceback + totals"), eng.tail_stage_last_ms()):
             timing[k] = timing.get(k, 0.0) + v * 1e-3
-    return dict(res=res, ext=ext, nodes=nodes, ext_total=ext_total, read_score=read_score, stats=stats, tails=tails, tail_ops=tail_ops)
+    return dict(res=res, ext=ext, nodes=nodes, mism=mism, ext_total=ext_total, read_score=read_score, stats=stats, tails=tails, tail_ops=tail_ops, composed=made)
+
+
+def read_alignments(eng, index, gs, stage, extension_score_threshold=1, max_local_extensions=0xffffffff, window_length=39):
+    """Giraffe's alignments per read (vgk_read_alignments) from what align_stage_device(..., aligned=True) returned for the reads of `gs`: the sets, and
+    the tails' winning alignments (`stage`'s res, ext, nodes, mism, tails, tail_ops).  -> dict(aln_off, alignments, mappings, edits, written)"""
+    return eng.read_alignments(index, gs.reads, gs.read_off, stage["res"], stage["ext"], stage["nodes"], stage["mism"], stage["tails"], stage["tail_ops"],
+                               extension_score_threshold, max_local_extensions, window_length)
+
+
+def read_alignments_gaf_view(reads, read_off, composed):
+    """What gaf_lines takes, from read_alignments' result: one record per ALIGNMENT — its read's bases (seqs, seq_off), the headers' leading
+    vgk_chain_result fields as CHAIN_RESULT_DT, and the scores.  -> (seqs, seq_off, results, score)"""
+    aln = composed["alignments"]
+    reads = np.ascontiguousarray(reads, dtype=np.uint8); off = np.ascontiguousarray(read_off, dtype=np.int64)
+    length = (off[1:] - off[:-1])[aln["read"]]
+    seq_off = np.concatenate([[0], np.cumsum(length)]).astype(np.uint64)
+    idx = np.repeat(off[:-1][aln["read"]], length) + (np.arange(int(length.sum())) - np.repeat(seq_off[:-1].astype(np.int64), length))
+    results = np.zeros(len(aln), dtype=capi.CHAIN_RESULT_DT)
+    for name in ("status", "mapping_begin", "n_mappings", "edit_begin", "n_edits", "from_length", "to_length"):
+        results[name] = aln[name]
+    return reads[idx], seq_off, results, aln["score"].astype(np.int32)
 
 
 def winning_alignments(out):

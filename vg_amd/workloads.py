@@ -1148,3 +1148,233 @@ class ExtensionAnchorsWorkload:
         seeds["node"] = raw["node"][keep]; seeds["diff"] = raw["diff"][keep]; seeds["stapled"] = stapled[keep]; seeds["length"] = self.k; seeds["is_reverse"] = rev[keep]; seeds["paths"] = 1
         seed_off = np.concatenate([[0], np.cumsum(np.bincount(read_of[keep], minlength=self.n))]).astype(np.uint64)
         return dict(reads=self.reads, read_off=self.read_off, seed_off=seed_off, seeds=seeds, dropped=int((~keep).sum()))
+
+
+class ReadAlignmentsWorkload:
+    """Extension sets and tail alignments for vgk_read_alignments (include/vgk_engine.h), fabricated directly — not through the aligner — so that every
+    branch of the rule can be planted.  The graph is a chain of sites: a node, a bubble of two alleles of EQUAL length, or a node every haplotype visits
+    twice in a row (a self-loop) — so every haplotype has the same coordinates, and an extension of a read interval lies on the same diagonal of any of
+    them.  A read is a stretch of one haplotype on either strand with a gapless middle and two tails made from ops (M with substitutions, I, D, a final
+    S); its set holds extensions over sub-intervals of the middle on any haplotype, each open end with the tail's ops (scored here) or a soft clip.
+    read_lengths / set_sizes: cycled over the reads.  -> nodes, threads, reads, read_off, res, ext, path_nodes, mism, tails, ops, oriented_len,
+    oriented_seq; steps: the (oriented, oriented) pairs a haplotype takes, on either strand."""
+
+    def __init__(self, n_reads, seed=0, read_lengths=(1, 2, 63, 64, 65, 127, 128, 129, 150, 200), set_sizes=(1, 2, 3, 4, 5), n_sites=150, n_haplotypes=4,
+                 scoring=(1, 4, 6, 1, 5), full_sets=0.2, n_rate=0.03):
+        rng = np.random.default_rng(seed)
+        self.scoring = tuple(int(x) for x in scoring)
+        comp = {"A": "T", "C": "G", "G": "C", "T": "A", "N": "N"}
+        rc = lambda s: "".join(comp[c] for c in reversed(s))
+        rand = lambda k: "".join("ACGT"[int(x)] for x in rng.integers(0, 4, k))
+        nodes, sites = [], []
+        for _ in range(n_sites):
+            kind = rng.random()
+            if kind < 0.25:                                   # a bubble of two equal-length alleles
+                k = int(rng.integers(1, 4)); a = rand(k); b = rand(k)
+                while b == a:
+                    b = rand(k)
+                nodes += [a, b]; sites.append(("bubble", len(nodes) - 2, len(nodes) - 1))
+            elif kind < 0.32:                                 # visited twice in a row
+                nodes.append(rand(int(rng.integers(1, 7)))); sites.append(("twice", len(nodes) - 1))
+            else:
+                nodes.append(rand(1 if rng.random() < 0.2 else int(rng.integers(2, 13)))); sites.append(("one", len(nodes) - 1))
+        threads = []
+        for h in range(n_haplotypes):
+            t = []
+            for s in sites:
+                if s[0] == "bubble":
+                    t.append(2 * s[1 + int(rng.integers(0, 2))] if h else 2 * s[1])
+                elif s[0] == "twice":
+                    t += [2 * s[1], 2 * s[1]]
+                else:
+                    t.append(2 * s[1])
+            threads.append(t)
+        self.nodes, self.threads = nodes, threads
+        oseq = []
+        for s in nodes:
+            oseq += [s, rc(s)]
+        self.oriented_len = np.array([len(s) for s in oseq], dtype=np.uint32)
+        self.oriented_seq = np.frombuffer("".join(oseq).encode(), dtype=np.uint8).copy()
+        walks = [[t, [o ^ 1 for o in reversed(t)]] for t in threads]          # [haplotype][strand] -> oriented nodes
+        self.steps = set()
+        for w in walks:
+            for s in w:
+                self.steps.update(zip(s[:-1], s[1:]))
+        # per strand: where in its (shared) coordinates every walk node begins
+        starts = []
+        for strand in range(2):
+            at = [0]
+            for o in walks[0][strand]:
+                at.append(at[-1] + len(oseq[o]))
+            starts.append(np.array(at, dtype=np.int64))
+        total = int(starts[0][-1])
+        strings = [["".join(oseq[o] for o in walks[h][s]) for s in range(2)] for h in range(n_haplotypes)]
+        match, mismatch, gap_open, gap_extend, bonus = self.scoring
+
+        def locate(strand, pos):                              # -> (index in the walk, offset) of coordinate pos
+            k = int(np.searchsorted(starts[strand], pos, side="right")) - 1
+            return k, pos - int(starts[strand][k])
+
+        def tail_ops(length):                                 # ops in tail order (from the extension outwards) spending `length` read bases
+            ops, left = [], length
+            style = int(rng.integers(0, 8))
+            if style == 0 and left >= 2:
+                k = int(rng.integers(1, min(left, 4))); ops.append((capi.OP_I, k)); left -= k
+            elif style == 1:
+                ops.append((capi.OP_D, int(rng.integers(1, 4))))
+            while left:
+                k = int(rng.integers(1, left + 1)); ops.append((capi.OP_M, k)); left -= k
+                if left and rng.random() < 0.5:
+                    what = int(rng.integers(0, 3))
+                    if what == 0:
+                        ops.append((capi.OP_D, int(rng.integers(1, 5))))
+                    elif what == 1:
+                        k = int(rng.integers(1, left + 1)); ops.append((capi.OP_I, k)); left -= k
+                        if not left:
+                            ops[-1] = (capi.OP_S, k)
+                    else:
+                        ops.append((capi.OP_S, left)); left = 0
+            return ops
+
+        def graph_bases(ops):
+            return sum(k for op, k in ops if op in (capi.OP_M, capi.OP_D))
+
+        reads, read_off, res, ext, path_nodes, mism, tails, ops_out = [], [0], [], [], [], [], [], []
+        for r in range(n_reads):
+            L = int(read_lengths[r % len(read_lengths)]); want = int(set_sizes[(r // len(read_lengths)) % len(set_sizes)])
+            hap, strand = int(rng.integers(0, n_haplotypes)), int(rng.integers(0, 2))
+            full_set = rng.random() < full_sets
+            m = L if full_set or rng.random() < 0.15 else int(rng.integers(1, L + 1))
+            a = int(rng.integers(0, L - m + 1)); b = L - m - a
+            lops, rops = (tail_ops(a) if a else []), (tail_ops(b) if b else [])
+            w0 = int(rng.integers(graph_bases(lops) + 8, total - m - graph_bases(rops) - 8))
+            S = strings[hap][strand]
+            # the read: the tails from their ops, the middle copied with a few substitutions
+            def spell(ops, pos, step):
+                out = []
+                for op, k in ops:
+                    if op == capi.OP_M:
+                        for _ in range(k):
+                            c = S[pos if step > 0 else pos - 1]; pos += step
+                            out.append(c if rng.random() > 0.08 else "ACGT"[("ACGT".index(c) + int(rng.integers(1, 4))) % 4])
+                    elif op == capi.OP_D:
+                        pos += step * k
+                    else:
+                        out.append(rand(k) if step > 0 else rand(k)[::-1])
+                return "".join(out)
+            mid = list(S[w0:w0 + m])
+            for k in range(m):
+                if rng.random() < 0.04 or (k in (0, m - 1) and rng.random() < 0.15) or (k and mid[k - 1] != S[w0 + k - 1] and rng.random() < 0.3):
+                    mid[k] = "ACGT"[("ACGT".index(mid[k]) + int(rng.integers(1, 4))) % 4]
+            read = spell(lops, w0, -1)[::-1] + "".join(mid) + spell(rops, w0 + m, 1)
+            assert len(read) == L
+            if rng.random() < n_rate:
+                k = int(rng.integers(0, L)); read = read[:k] + "N" + read[k + 1:]
+            reads.append(read); read_off.append(read_off[-1] + L)
+
+            def make_tail(e_index, h2, left, begin, end, ops, pos):
+                """ops in tail order from coordinate pos (a left tail walks down from pos - 1, on the other strand); None when it does not score above 0"""
+                T = strings[h2][strand]; walk = walks[h2][strand]
+                recs, score, q = [], 0, 0
+                seq = read[begin:end][::-1] if left else read[begin:end]          # bases in tail order (complemented on both sides alike for a left tail: compare as they are)
+                k0, off0 = locate(strand, pos - 1 if left else pos)
+                first_offset = (len(oseq[walk[k0]]) - 1 - off0) if left else off0
+                cur = k0
+                for op, k in ops:
+                    if op in (capi.OP_M, capi.OP_D):
+                        gap = op == capi.OP_D
+                        if gap:
+                            score -= gap_open + (k - 1) * gap_extend
+                        while k:
+                            p = pos - 1 if left else pos
+                            cur, off = locate(strand, p)
+                            room = (off + 1) if left else (len(oseq[walk[cur]]) - off)
+                            step = min(k, room)
+                            if not gap:
+                                for j in range(step):
+                                    c = T[p - j] if left else T[p + j]
+                                    score += match if seq[q + j] == c else -mismatch
+                                q += step
+                            recs.append((walk[cur] ^ 1 if left else walk[cur], step, op))
+                            pos += -step if left else step; k -= step
+                    else:
+                        if op == capi.OP_I:
+                            score -= gap_open + (k - 1) * gap_extend
+                        recs.append((walk[cur] ^ 1 if left else walk[cur], k, op)); q += k
+                if ops[-1][0] != capi.OP_S:
+                    score += bonus
+                if score <= 0:
+                    return None
+                merged = []
+                for node, k, op in recs:                     # runs of one kind on one visit are one op
+                    merged.append((node, k, op))
+                return dict(ext=e_index, left=left, read_begin=begin, read_end=end, score=score, first_offset=first_offset, ops=merged)
+
+            def make_ext(h2, rb2, re2):
+                T = strings[h2][strand]; walk = walks[h2][strand]
+                p0 = w0 + (rb2 - a); k0, off0 = locate(strand, p0); k1, _ = locate(strand, p0 + (re2 - rb2) - 1)
+                mm = [p for p in range(rb2, re2) if read[p] != T[w0 + (p - a)]]
+                lf, rf = rb2 == 0, re2 == L
+                score = (re2 - rb2 - len(mm)) * match - len(mm) * mismatch + bonus * (int(lf) + int(rf))
+                return dict(path=walk[k0:k1 + 1], offset=off0, read_begin=rb2, read_end=re2, mism=mm, score=score, left_full=lf, right_full=rf, hap=h2)
+
+            made = [make_ext(hap, a, a + m)]
+            while len(made) < want:
+                h2 = int(rng.integers(0, n_haplotypes))
+                if full_set and len(made) < 3 and rng.random() < 0.7 and a == 0 and m == L:
+                    made.append(make_ext(h2, 0, L)); continue
+                if rng.random() < 0.25:
+                    made.append(make_ext(h2, a, a + m)); continue
+                x = int(rng.integers(a, a + m)); y = int(rng.integers(x + 1, a + m + 1))
+                made.append(make_ext(h2, x, y))
+            full = [e for e in made if e["left_full"] and e["right_full"]]
+            part = [e for e in made if not (e["left_full"] and e["right_full"])]
+            full.sort(key=lambda e: len(e["mism"]))
+            made = full + part
+            res.append((0, len(ext), len(made), 1 if full and len(full[0]["mism"]) <= 4 else 0))
+            for e in made:
+                x = len(ext)
+                ext.append((len(path_nodes), len(e["path"]), e["offset"], e["read_begin"], e["read_end"], len(mism), len(e["mism"]), e["score"], int(e["left_full"]), int(e["right_full"])))
+                path_nodes += e["path"]; mism += e["mism"]
+                for left in (0, 1):
+                    if (e["left_full"] if left else e["right_full"]):
+                        continue
+                    how = rng.random()
+                    if how < 0.25:
+                        continue                               # no entry: the soft clip
+                    if left:
+                        t = make_tail(x, e["hap"], 1, 0, e["read_begin"], ([(capi.OP_M, e["read_begin"] - a)] if e["read_begin"] > a else []) + lops, w0 + (e["read_begin"] - a))
+                    else:
+                        t = make_tail(x, e["hap"], 0, e["read_end"], L, ([(capi.OP_M, a + m - e["read_end"])] if e["read_end"] < a + m else []) + rops, w0 + (e["read_end"] - a))
+                    if t is None or how < 0.35:
+                        t = dict(ext=x, left=left, read_begin=0 if left else e["read_end"], read_end=e["read_begin"] if left else L, score=0, first_offset=0, ops=[])
+                    tails.append(t)
+        tails.sort(key=lambda t: (t["left"], t["ext"]))         # right tails by extension, then left tails: the tail stage's order
+        self.n = n_reads
+        self.reads = np.frombuffer("".join(reads).encode(), dtype=np.uint8).copy(); self.read_off = np.array(read_off, dtype=np.uint64)
+        self.read_strings = reads
+        self.res = np.array(res, dtype=capi.GAPLESS_RESULT_DT) if res else np.zeros(0, dtype=capi.GAPLESS_RESULT_DT)
+        self.ext = np.zeros(len(ext), dtype=capi.EXT_DT)
+        for k, name in enumerate(("path_begin", "path_len", "offset", "read_begin", "read_end", "mism_begin", "n_mismatches", "score", "left_full", "right_full")):
+            self.ext[name] = [e[k] for e in ext]
+        self.path_nodes = np.array(path_nodes, dtype=np.uint32); self.mism = np.array(mism, dtype=np.uint32)
+        self.tails = np.zeros(len(tails), dtype=capi.TAIL_ALIGNMENT_DT)
+        flat = []
+        for k, t in enumerate(tails):
+            self.tails[k] = (t["ext"], t["left"], t["read_begin"], t["read_end"], t["score"], 0, len(flat), len(t["ops"]), t["first_offset"], 1 if t["ops"] else 0)
+            flat += t["ops"]
+        self.ops = np.zeros(len(flat), dtype=capi.OP_DT)
+        if flat:
+            self.ops["node"] = [o[0] for o in flat]; self.ops["len"] = [o[1] for o in flat]; self.ops["op"] = [o[2] for o in flat]
+
+    def tiled(self, times):
+        """the call's arrays with the reads repeated `times` times: every copy has its own extensions and tails, all share the path nodes, mismatches and ops"""
+        res = np.tile(self.res, times); ext = np.tile(self.ext, times); tails = np.tile(self.tails, times)
+        res["ext_begin"] += np.repeat(np.arange(times, dtype=np.uint32) * len(self.ext), len(self.res)).astype(np.uint32)
+        tails["ext"] += np.repeat(np.arange(times, dtype=np.uint32) * len(self.ext), len(self.tails)).astype(np.uint32)
+        lengths = np.tile(np.diff(self.read_off.astype(np.int64)), times)
+        return dict(reads=np.tile(self.reads, times), read_off=np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64), results=res, extensions=ext, nodes=self.path_nodes,
+                    mismatches=self.mism, tails=tails, ops=self.ops)
+
+    def call_arrays(self):
+        return dict(reads=self.reads, read_off=self.read_off, results=self.res, extensions=self.ext, nodes=self.path_nodes, mismatches=self.mism, tails=self.tails, ops=self.ops)
