@@ -58,8 +58,39 @@ struct TbStage {
     }
 };
 
+// The walks at the end of a speculative batch's second fill (GsswParams::refill_walk; the NOKEY kernels below): lane s < 2 * (64 / G) takes the s-th read of its
+// wavefront's pairs, the end cell the first fill's.  Everything the walks need — the parameter block, the wavefront, the lane — is read afresh here, through a
+// copy of the kernel-argument pointer the optimiser cannot see through: nothing of it is live across the step loop, whose registers and instructions stay what
+// they are without the walks.  (GsswParams is the kernel's only argument: the block starts at the segment's first byte.)
+static __device__ __forceinline__ void refill_walk_own_reads(uint32_t wave) {
+    typedef __attribute__((address_space(4))) const GsswParams KernArgs;
+    KernArgs* kp = (KernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    GsswParams P;
+    __builtin_memcpy(&P, kp, sizeof P);
+    if (!P.refill_walk) return;
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));      // (threadIdx.x & 63, without the register that holds threadIdx.x)
+    const WaveDesc wd = P.waves[wave];
+    // This wave's traceback codes / scratch columns -> visible to its walker lanes, which are lanes of the SAME wavefront: its stores have left for the L2
+    // its loads go to (the CU's vector cache writes through) once they are waited for — a fence at workgroup scope.  __threadfence(), the agent-scope fence
+    // of the whole-batch fused path below, also writes the L2's dirty lines back for the other dies' sake: with every wavefront of a fill that streams
+    // codes out doing so, the second fill went from 1.37 to 2.91 ms per million reads (profiles/r10_refill_walk).
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    const uint32_t n_slots = 2u * (64u / wd.G);
+    for (uint32_t slot = lane; slot < n_slots; slot += 64u) {
+        const uint32_t pair = wd.first_pair + (slot >> 1);
+        if (pair >= wd.pair_end) continue;
+        const uint32_t prob = P.order[2u * pair + (slot & 1u)];
+        if (prob != 0xffffffffu) walk_one(P, prob, P.best[prob]);
+    }
+}
+
 // CODES = false: the recurrence alone and nothing of a traceback (GsswParams::spec_fill's first fill)
-// NOKEY: the second fill of a speculative batch (spec_fill == 2) — codes only; the end cells are the first fill's, nothing is tracked or published
+// NOKEY: the second fill of a speculative batch (spec_fill == 2) — codes only; the end cells are the first fill's, nothing is tracked or published.
+//        With GsswParams::refill_walk each wavefront then walks the reads it filled (refill_walk_own_reads) and no gssw_walk_missed_kernel follows: a
+//        wavefront's sixteen walks wait for their codes while the other wavefronts of its SIMD issue rows.  Built, exact, and OFF by default: on the MI355X
+//        the fill with its walks takes 2.43 ms per million reads against 1.11 + 0.87 ms for the two kernels (profiles/r10_refill_walk) — 16 of 64 lanes hold a
+//        168-register wavefront slot for the length of a walk, and the separate kernel's 2 000 wavefronts overlap their fetches better than that.
 // OFFS: a KEY3 first fill whose rows run in the offset form (gssw_device.hpp: gssw_row_offset; GsswParams::row_off != 0)
 template <int K, bool S8, bool REWALK, bool CODES = true, bool KEY3 = false, bool NOKEY = false, bool OFFS = false>
 __global__ __launch_bounds__(256, (K <= 16 ? 4 : 3)) void gssw_fill_kernel(const GsswParams P) {
@@ -70,6 +101,8 @@ __global__ __launch_bounds__(256, (K <= 16 ? 4 : 3)) void gssw_fill_kernel(const
     if (wave >= P.wave_begin + P.wave_count) return;
     if (P.wave_limit && wave - P.wave_begin >= *P.wave_limit) return;
     const WaveDesc wd = P.waves[wave];
+    uint32_t wave_s = 0;             // (NOKEY: for the walks behind the step loop, in a scalar register)
+    if constexpr (NOKEY) wave_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);
     Lane<K> s;
 #if VGK_PB_LDS
     __shared__ uint32_t pb_lds[4][64 * K];      // read B's profile words, [row][lane] per wavefront (gssw_device.hpp: VGK_PB_LDS)
@@ -141,7 +174,7 @@ __global__ __launch_bounds__(256, (K <= 16 ? 4 : 3)) void gssw_fill_kernel(const
         } else
             lane_step<K, S8, true, false, NOKEY, false, 0>(s, P, t, rh, rf, ri, tb ? tb + tb_dword(wd.tb_off, t, lane, REC, 0) : nullptr, tb ? tb + tb_dword(wd.tb_off, t, lane, REC, 4) : nullptr);
     }
-    if constexpr (NOKEY) return;
+    if constexpr (NOKEY) { refill_walk_own_reads(wave_s); return; }
     if (REWALK || !CODES || !P.fused) {
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
@@ -209,8 +242,21 @@ __global__ __launch_bounds__(64) void gssw_walk_first_kernel(const GsswParams P,
     const uint32_t i = P.order[k];
     if (i != 0xffffffffu) walk_first_one(P, i, P.best[i], blk + threadIdx.x, 64, tab);
 }
-__global__ __launch_bounds__(64) void gssw_refill_layout_kernel(const GsswParams P) {
-    refill_layout_one(P, blockIdx.x * blockDim.x + threadIdx.x);
+// a lane per read slot of the miss list (gssw_device.hpp: refill_layout_read): the 2 * 64 / G slots of one second-fill wavefront in neighbouring lanes — a
+// group of min(slots, 64) lanes, a lane of it taking every 64th slot where there are more —, the widest column range by shuffles inside the group, the
+// wavefront's descriptor from the group's first lane.  A wavefront of this kernel lays out 64 / group second-fill wavefronts.
+__host__ __device__ static inline uint32_t refill_layout_group(uint32_t G) { const uint32_t slots = 2u * (64u / G); return slots < 64u ? slots : 64u; }
+__global__ __launch_bounds__(256) void gssw_refill_layout_kernel(const GsswParams P) {
+    const uint32_t lane = threadIdx.x & 63u, slots = 2u * (64u / P.refill_G), group = refill_layout_group(P.refill_G), per_wave = 64u / group;
+    const uint32_t q = lane / group, at = lane - q * group;
+    const uint32_t w2 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * per_wave + q;
+    const uint32_t M = *tb_miss_count(P);
+    uint32_t rmax = 0;
+    if (q < per_wave)
+        for (uint32_t s = at; s < slots; s += group) { const uint32_t cols = refill_layout_read(P, M, w2 * slots + s); rmax = cols > rmax ? cols : rmax; }
+#pragma unroll
+    for (uint32_t d = 32; d > 0; d >>= 1) { const uint32_t o = (uint32_t)__shfl_down((int)rmax, d, 64); if (at + d < group && o > rmax) rmax = o; }
+    if (q < per_wave && at == 0) refill_layout_wave(P, M, w2, rmax);
 }
 __global__ __launch_bounds__(256) void gssw_refill_restore_kernel(const GsswParams P) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1711,6 +1757,9 @@ public:
         hipSetDevice(dev);
         return hipMemsetAsync(dst, byte, bytes, copy) == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
+    // whether a speculative batch's second fill runs the kernels of its own (NOKEY: codes only, reads begun at their col0, and — GsswParams::refill_walk —
+    // the walks of its reads): the x8 scale on stored codes; unscaled scorings, TB_REWALK and `fused` batches run it through the plain kernels
+    static bool refill_own_kernel(const GsswParams& p) { return p.spec_fill == 2 && p.scale == 8 && p.tb_mode != TB_REWALK && !p.fused; }
     template <int K> int launch_fill_k(const GsswParams& p, hipStream_t stream) {
         const dim3 grid((p.wave_count + 3) / 4), block(256);
         const bool s8 = p.scale == 8, re = p.tb_mode == TB_REWALK;
@@ -1720,7 +1769,7 @@ public:
             else if (s8) hipLaunchKernelGGL((gssw_fill_kernel<K, true, false, false>), grid, block, 0, stream, p); else hipLaunchKernelGGL((gssw_fill_kernel<K, false, false, false>), grid, block, 0, stream, p);
             return VGK_OK;
         }
-        if (p.spec_fill == 2 && s8 && !re && !p.fused) { hipLaunchKernelGGL((gssw_fill_kernel<K, true, false, true, false, true>), grid, block, 0, stream, p); return VGK_OK; }      // (codes only: the end cells are the first fill's)
+        if (refill_own_kernel(p)) { hipLaunchKernelGGL((gssw_fill_kernel<K, true, false, true, false, true>), grid, block, 0, stream, p); return VGK_OK; }      // (codes only: the end cells are the first fill's)
         if (re) { if (s8) hipLaunchKernelGGL((gssw_fill_kernel<K, true, true>), grid, block, 0, stream, p); else hipLaunchKernelGGL((gssw_fill_kernel<K, false, true>), grid, block, 0, stream, p); }
         else    { if (s8) hipLaunchKernelGGL((gssw_fill_kernel<K, true, false>), grid, block, 0, stream, p); else hipLaunchKernelGGL((gssw_fill_kernel<K, false, false>), grid, block, 0, stream, p); }
         return VGK_OK;
@@ -1755,11 +1804,13 @@ public:
                     const uint32_t max_waves = (p0.n_pairs + 64u / p0.refill_G - 1u) / (64u / p0.refill_G);
                     for (int k = 0; k < 2; ++k) if (!sev[lane][k]) hipEventCreate(&sev[lane][k]);
                     hipEventRecord(sev[lane][0], stream);
-                    hipLaunchKernelGGL(gssw_refill_layout_kernel, dim3((max_waves + 63) / 64), dim3(64), 0, stream, p0);
+                    const uint32_t per_block = 4u * (64u / refill_layout_group(p0.refill_G));      // second-fill wavefronts a block of the layout lays out
+                    hipLaunchKernelGGL(gssw_refill_layout_kernel, dim3((max_waves + per_block - 1u) / per_block), dim3(256), 0, stream, p0);
                     GsswParams p = p0;
                     p.spec_fill = 2; p.K = p0.refill_K; p.wave_begin = p0.refill_wave0; p.wave_count = max_waves; p.wave_limit = p0.refill_count;
                     launch_fill(p, stream);
                     hipEventRecord(sev[lane][1], stream); sev_set[lane] = true;
+                    if (refill_own_kernel(p) && p.refill_walk) return;      // (its wavefronts have walked their reads)
                 }
                 hipLaunchKernelGGL(gssw_walk_missed_kernel, dim3((p0.n_problems + 255) / 256), dim3(256), 0, stream, p0);      // (lanes beyond the list's end leave at once)
             } else hipLaunchKernelGGL(gssw_walk_kernel, dim3((2 * p0.n_pairs + 255) / 256), dim3(256), 0, stream, p0, walk_in_fill_order ? 1 : 0);
@@ -1780,7 +1831,8 @@ public:
     }
     // One fill launch per rows-per-lane instantiation K (lanes-per-pair G is a per-wavefront value), then one traceback launch over all
     // reads.  (Running walk(c) under fill(c+1) on a second stream, and fusing the walk into the fill kernel,
-    // were both measured slower than this plain sequence on MI355X — DESIGN.md §5; `fused` is kept as an option.)
+    // were both measured slower than this plain sequence on MI355X — DESIGN.md §5; `fused` is kept as an option.  That was the whole-batch fill; the
+    // second fill of a speculative batch walking its own reads, GsswParams::refill_walk, was measured on its own and is slower too: DESIGN.md §3a.)
     int run_gssw(const GsswParams& p0, const FillLaunch* launches, uint32_t n, bool walk) override {
         hipSetDevice(dev);
         n_launches = n ? (int)n : 1;

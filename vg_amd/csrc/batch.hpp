@@ -67,6 +67,16 @@ inline void set_refill_bound(GsswParams& P, const vgk_ctx* ctx) {
     P.refill_m = (uint32_t)std::max(0, ctx->max_score) * ctx->scale;
 }
 
+// The wavefronts of a speculative batch's second fill can walk their own reads back (GsswParams::refill_walk) instead of leaving them to
+// gssw_walk_missed_kernel.  Measured on the MI355X it does not pay (profiles/r10_refill_walk: the fill with its walks 2.43 ms per million reads against
+// 1.11 + 0.87 ms for the two kernels), so the field is 0 unless VGAMD_REFILL_WALK=1 is set when the batch is packed; VGAMD_NO_REFILL_WALK=1 leaves it 0
+// whatever else is set (A/B runs on one library).
+inline void set_refill_walk(GsswParams& P) {
+    const char* on = std::getenv("VGAMD_REFILL_WALK");
+    const char* off = std::getenv("VGAMD_NO_REFILL_WALK");
+    P.refill_walk = P.spec_fill && on && std::atoi(on) && !(off && std::atoi(off)) ? 1 : 0;
+}
+
 template <class T>
 inline int to_device(vgk_batch* b, const std::vector<T>& v, const T*& out, size_t extra = 0) {
     const size_t bytes = (v.size() + extra) * sizeof(T);

@@ -58,7 +58,7 @@ struct ProbDesc {          // one per read
     uint32_t n_nodes;
     uint32_t scratch_off;  // u32 index of this read's boundary scratch (16-aligned)
     uint32_t n_slots;
-    uint32_t flags;        // VGK_GSSW_*
+    uint32_t flags;        // VGK_GSSW_* | PD_CHAIN
     uint32_t ops_off;      // first vgk_op of this read's output window
     uint32_t ops_cap;
     uint32_t max_gap;      // XDROP: leading-insertion cells of the root column (dz_align_init), multiple of 8
@@ -76,6 +76,11 @@ struct ProbDesc {          // one per read
     // node0 nodes begun before it; both 0 everywhere else (the packers, refill_restore_one)
     uint32_t col0, node0;
 };
+
+// ProbDesc::flags, the packers' own bit (include/vgk.h gives callers bits 0 - 4; a caller's bit 31 is dropped): a LOCAL read whose window is a CHAIN — every
+// node's only predecessor is the node before it, the first node has none.  A property of the packed window, decided once when the batch is packed:
+// refill_col0 reads it on every speculative run of the resident batch.
+constexpr uint32_t PD_CHAIN = 0x80000000u;
 
 struct NodeRec {
     uint32_t col_start;    // first column
@@ -142,7 +147,10 @@ struct GsswParams {
     uint32_t xoff;              // XOFF * scale
     int8_t   matrix[25];
     uint32_t row_off;           // a key3 batch's first fill runs its rows in the offset form (lane_row): every H / E / F of that fill carries this constant (scaled;
-                                // gssw_row_offset), 0 = the saturating rows.  (Last: no other field moves.)
+                                // gssw_row_offset), 0 = the saturating rows.  (Behind everything older: no other field moves.)
+    int32_t  refill_walk;       // the second fill's wavefronts walk their own reads back at the end of the fill kernel (backend_hip.hip: the NOKEY kernels) and no
+                                // gssw_walk_missed_kernel follows; 0, the default (batch.hpp: VGAMD_REFILL_WALK=1 sets it, measured slower): the separate kernel, as
+                                // for unscaled scorings and `fused` batches, whose second fill runs the plain kernels
 };
 
 VGK_HD uint32_t rep2(uint32_t x) { return (x & 0xffffu) * 0x00010001u; }
@@ -1326,67 +1334,71 @@ VGK_HD void tb_bound_broken(const GsswParams& P) {
 // bonuses - S - go) / gx) (0 when the numerator is negative) and the path lies in columns [c_e - r_e - D_max, c_e].  A recurrence begun there with
 // zeros never exceeds the true values and equals them on every co-optimal path, all of which lie inside: every maximum a walk consults has the
 // same winners, so the codes it reads are the full fill's.  Rounded down to a dword of the column stream.  0 — no bound —
-// for gx = 0 and for windows that are no chain, where column indices span more than a path does.  node0 = the nodes begun before that column.
+// for gx = 0 and for windows that are no chain (PD_CHAIN), where column indices span more than a path does.  node0 = the nodes begun before that column.
 VGK_HD uint32_t refill_col0(const GsswParams& P, const ProbDesc& d, unsigned long long key, uint32_t& node0) {
     node0 = 0;
     const uint32_t S = (uint32_t)(key >> 40), c_e = 0xFFFFFu - (uint32_t)((key >> 20) & 0xFFFFFu), r_e = 0xFFFFFu - (uint32_t)(key & 0xFFFFFu);
     const uint32_t gx = P.go < P.ge ? P.go : P.ge;
-    if (!S || !gx || r_e >= d.L || c_e >= d.R) return 0;
+    if (!(d.flags & PD_CHAIN) || !S || !gx || r_e >= d.L || c_e >= d.R) return 0;      // (whether the window is a chain: the packers' answer)
     const long long num = (long long)P.refill_m * (r_e + 1u) + d.bonus_start + d.bonus_end - (long long)S * P.scale - P.go;
     const unsigned long long span = (unsigned long long)r_e + (num < 0 ? 0ull : 1ull + (unsigned long long)num / gx);
     if (span >= c_e) return 0;
     const uint32_t col0 = (c_e - (uint32_t)span) & ~3u;
     if (!col0) return 0;
+    // the nodes that begin left of col0: first columns ascend and node 0's is 0 < col0 — the last such node by bisection, a handful of dependent loads
     const NodeRec* nodes = P.nodes + d.node_off;
-    uint32_t begun = 0;
-    for (uint32_t n = 0; n < d.n_nodes; ++n) {
-        const NodeRec nr = nodes[n];
-        if (nr.pinning || (n ? nr.n_pred != 1u || P.preds[nr.pred_begin] != n - 1u : nr.n_pred != 0u)) return 0;
-        begun += nr.col_start < col0 ? 1u : 0u;
-    }
-    node0 = begun;
+    uint32_t lo = 0, hi = d.n_nodes;
+    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (nodes[mid].col_start < col0) lo = mid; else hi = mid; }
+    node0 = lo + 1u;
     return col0;
 }
-// one wavefront of the second fill (GsswParams::spec_fill): the reads at [16 w2 .. ) of the miss list, two to a lane group as in the batch's own
-// wavefronts (vgk_api.cpp / gssw_pack_device.hpp build those); the reads' descriptors learn where their codes will lie
-VGK_HD void refill_layout_one(const GsswParams& P, uint32_t w2) {
-    const uint32_t M = *tb_miss_count(P), G = P.refill_G, gpw = 64u / G;
+// The layout of the second fill (GsswParams::spec_fill): wavefront w2 takes the reads at [2 gpw w2 .. ) of the miss list, gpw = 64 / G pairs, two reads to a
+// lane group as in the batch's own wavefronts (vgk_api.cpp / gssw_pack_device.hpp build those).  Two parts: per read SLOT k of the miss list — the read's
+// descriptor learns where its codes will lie, order[] its entry — and per wavefront, from the widest of its reads' column ranges.  The kernel runs a lane per
+// slot (backend_hip.hip); refill_layout_one is their serial composition.
+// -> the columns the read's second fill runs over, 0 for a slot without a read
+VGK_HD uint32_t refill_layout_read(const GsswParams& P, uint32_t M, uint32_t k) {
+    const uint32_t G = P.refill_G, gpw = 64u / G, pair = k >> 1, h = k & 1u, w2 = pair / gpw, q = pair - w2 * gpw;
+    if (pair >= (M + 1u) / 2u) return 0;
+    const uint32_t i = k < M ? tb_miss_list(P)[k] : 0xffffffffu;
+    const_cast<uint32_t*>(P.order)[2u * (size_t)P.refill_pair0 + k] = i;
+    if (i == 0xffffffffu) return 0;
+    ProbDesc& d = const_cast<ProbDesc*>(P.probs)[i];                  // (the batch's own device array)
+    // a traceback never looks right of its end cell, and a LOCAL alignment's end cell is known (the first fill's best key): the second
+    // fill of such a read stops behind that column.  Its own best key is then the maximum over fewer cells — the same cell, first among
+    // equals as before — and atomicMax leaves best[] as it is.
+    // Nor does it look left of refill_col0's column: the fill starts there, and the wavefront runs as long as its widest such range.
+    uint32_t cols = d.R, col0 = 0, node0 = 0;
+    const uint32_t flags = d.flags;
+    if ((flags & 15u) == (uint32_t)VGK_GSSW_LOCAL) {
+        const unsigned long long key = P.best[i];
+        const uint32_t c_e = 0xFFFFFu - (uint32_t)((key >> 20) & 0xFFFFFu);
+        if (c_e + 1u < cols) cols = c_e + 1u;
+        if (P.refill_bound && (flags & VGK_GSSW_TRACEBACK)) col0 = refill_col0(P, d, key, node0);
+    }
+    d.col0 = col0; d.node0 = node0;
+    // (where the batch's own fill put the read: kept in the descriptor's spare word, for a later run of this resident batch WITHOUT the
+    // speculation — vgk_gssw_run's feedback may decide so — which refill_restore_one hands it back to.  Only the first displacement saves.)
+    if (!(d.pad & 0x80000000u)) d.pad = 0x80000000u | (d.wave & 0xffffffu) | ((d.lane0 & 63u) << 24) | (((d.geom >> 16) & 1u) << 30);
+    d.wave = P.refill_wave0 + w2; d.lane0 = q * G; d.geom = P.refill_K | (G << 8) | (h << 16);
+    return cols - col0;
+}
+// rmax = the maximum of refill_layout_read over the wavefront's 2 gpw slots
+VGK_HD void refill_layout_wave(const GsswParams& P, uint32_t M, uint32_t w2, uint32_t rmax) {
+    const uint32_t G = P.refill_G, gpw = 64u / G;
     const uint32_t n_pairs2 = (M + 1u) / 2u, n_waves2 = (n_pairs2 + gpw - 1u) / gpw;
     if (w2 == 0) P.refill_count[0] = n_waves2;
     if (w2 >= n_waves2) return;
-    const uint32_t* list = tb_miss_list(P);
-    ProbDesc* probs = const_cast<ProbDesc*>(P.probs);                 // (the batch's own device array)
-    uint32_t* order = const_cast<uint32_t*>(P.order);
-    WaveDesc* waves = const_cast<WaveDesc*>(P.waves);
     WaveDesc wd; wd.first_pair = P.refill_pair0 + w2 * gpw; wd.G = G; wd.pair_end = P.refill_pair0 + n_pairs2;
-    uint32_t rmax = 0;
-    for (uint32_t q = 0; q < gpw; ++q) for (uint32_t h = 0; h < 2u; ++h) {
-        const uint32_t k = 2u * (w2 * gpw + q) + h;
-        const uint32_t i = k < M ? list[k] : 0xffffffffu;
-        if (w2 * gpw + q < n_pairs2) order[2u * (size_t)P.refill_pair0 + k] = i;
-        if (i == 0xffffffffu) continue;
-        ProbDesc& d = probs[i];
-        // a traceback never looks right of its end cell, and a LOCAL alignment's end cell is known (the first fill's best key): the second
-        // fill of such a read stops behind that column.  Its own best key is then the maximum over fewer cells — the same cell, first among
-        // equals as before — and atomicMax leaves best[] as it is.
-        // Nor does it look left of refill_col0's column: the fill starts there, and the wavefront runs as long as its widest such range.
-        uint32_t cols = d.R;
-        d.col0 = 0; d.node0 = 0;
-        if ((d.flags & 15u) == (uint32_t)VGK_GSSW_LOCAL) {
-            const unsigned long long key = P.best[i];
-            const uint32_t c_e = 0xFFFFFu - (uint32_t)((key >> 20) & 0xFFFFFu);
-            if (c_e + 1u < cols) cols = c_e + 1u;
-            if (P.refill_bound && (d.flags & VGK_GSSW_TRACEBACK)) d.col0 = refill_col0(P, d, key, d.node0);
-        }
-        rmax = cols - d.col0 > rmax ? cols - d.col0 : rmax;
-        // (where the batch's own fill put the read: kept in the descriptor's spare word, for a later run of this resident batch WITHOUT the
-        // speculation — vgk_gssw_run's feedback may decide so — which refill_restore_one hands it back to.  Only the first displacement saves.)
-        if (!(d.pad & 0x80000000u)) d.pad = 0x80000000u | (d.wave & 0xffffffu) | ((d.lane0 & 63u) << 24) | (((d.geom >> 16) & 1u) << 30);
-        d.wave = P.refill_wave0 + w2; d.lane0 = q * G; d.geom = P.refill_K | (G << 8) | (h << 16);
-    }
     wd.n_steps = rmax ? rmax + G - 1u : 0u;
     wd.tb_off = (unsigned long long)w2 * P.refill_slot;
-    waves[P.refill_wave0 + w2] = wd;
+    const_cast<WaveDesc*>(P.waves)[P.refill_wave0 + w2] = wd;
+}
+VGK_HD void refill_layout_one(const GsswParams& P, uint32_t w2) {
+    const uint32_t M = *tb_miss_count(P), slots = 2u * (64u / P.refill_G);
+    uint32_t rmax = 0;
+    for (uint32_t s = 0; s < slots; ++s) { const uint32_t cols = refill_layout_read(P, M, w2 * slots + s); rmax = cols > rmax ? cols : rmax; }
+    refill_layout_wave(P, M, w2, rmax);
 }
 // a read an earlier speculative run displaced goes back to the wavefront, lane group and half the batch's own fill gives it
 VGK_HD void refill_restore_one(const GsswParams& P, uint32_t i) {

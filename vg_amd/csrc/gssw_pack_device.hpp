@@ -224,7 +224,7 @@ VGK_HD void ext_size_one(const WinParams& P, uint32_t i, WinAcc& acc) {
     } else {
         uint32_t K, G; lane_geometry(rows, P.forced_k, K, G);
         const uint32_t nn = count ? count : 1u;
-        d.R = R; d.L = rows; d.n_nodes = nn; d.n_slots = slots; d.flags = p.flags;
+        d.R = R; d.L = rows; d.n_nodes = nn; d.n_slots = slots; d.flags = p.flags & ~PD_CHAIN;
         d.node_off = p.first_node;
         d.max_gap = ((p.max_gap_length > 1u ? p.max_gap_length : 1u) + 7u) & ~7u;
         d.geom = K | (G << 8); d.Lpad = G * K;
@@ -275,8 +275,18 @@ VGK_HD void win_size_one(const WinParams& P, uint32_t i, WinAcc& acc) {
         key = ((WIN_BUCKETS - 1) << 16) | 0xffffu;
     } else {
         uint32_t K, G; lane_geometry(rows, P.forced_k, K, G);
-        d.R = R; d.L = rows; d.n_nodes = p.n_nodes; d.n_slots = slots; d.flags = p.flags;
+        d.R = R; d.L = rows; d.n_nodes = p.n_nodes; d.n_slots = slots; d.flags = p.flags & ~PD_CHAIN;
         d.node_off = p.first_node;                      // until win_emit_one places the problem's NodeRecs
+        if (mode == VGK_GSSW_LOCAL) {                   // a chain (PD_CHAIN), over the predecessors INSIDE the window as win_emit_one keeps them: the first node has none,
+            const uint32_t a = p.first_node;            // every other node exactly the node before it
+            bool chain = true;
+            for (uint32_t v = a; chain && v < a + p.n_nodes; ++v) {
+                uint32_t np = 0, last = 0;
+                for (uint32_t e = P.g.pred_off[v]; e < P.g.pred_off[v + 1]; ++e) { const uint32_t q = P.g.pred_idx[e]; if (q >= a) { ++np; last = q; } }
+                chain = v == a ? np == 0u : (np == 1u && last + 1u == v);
+            }
+            if (chain) d.flags |= PD_CHAIN;
+        }
         d.max_gap = xdrop ? (((p.max_gap_length > 1u ? p.max_gap_length : 1u) + 7u) & ~7u) : 0u;
         d.geom = K | (G << 8); d.Lpad = G * K;
         d.bonus_start = xdrop ? 0u : (uint32_t)P.bonus * P.scale;

@@ -176,7 +176,7 @@ int vgk_gssw_pack(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_t n, ui
         if (xdrop && (int64_t)p.read_len * std::max(ctx->max_score, 0) + ctx->max_bonus >= (int64_t)XOFF) { z.status = VGK_EUNSUPPORTED; return; }
         if ((ctx->has_qa && !p.qual) || (mode == VGK_GSSW_PINNED && !p.pinning) || !g.node_len || !g.pred_off || !g.seq) { z.status = VGK_EINVAL; return; }
         z.want_tb = (p.flags & VGK_GSSW_TRACEBACK) != 0;
-        d.flags = p.flags; d.L = p.read_len + (xdrop ? 1u : 0u); d.n_nodes = g.n_nodes;
+        d.flags = p.flags & ~PD_CHAIN; d.L = p.read_len + (xdrop ? 1u : 0u); d.n_nodes = g.n_nodes;
         d.max_gap = xdrop ? ((std::max<uint32_t>(p.max_gap_length, 1u) + 7u) & ~7u) : 0u;
         {   // which full-length bonuses this problem grants, and their values (src/aligner.cpp:401-402, 942-952, 1164-1167)
             const uint32_t S = ctx->scale;
@@ -188,6 +188,11 @@ int vgk_gssw_pack(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_t n, ui
         }
         Flags& f = thread_flags[t];
         if ((z.status = node_flags(p, xdrop, mode, f)) != VGK_OK) return;
+        if (mode == VGK_GSSW_LOCAL) {                            // a chain (PD_CHAIN): node 0 has no predecessor, every other node's first column is no slow seed
+            bool chain = g.pred_off[1] == g.pred_off[0];
+            for (uint32_t v = 1; chain && v < g.n_nodes; ++v) chain = !f.slow[v];
+            if (chain) d.flags |= PD_CHAIN;
+        }
         uint64_t col = 0; uint32_t slots = 0;
         f.col_end.resize(g.n_nodes);
         for (uint32_t v = 0; v < g.n_nodes; ++v) {
@@ -479,6 +484,7 @@ int vgk_gssw_pack(vgk_ctx* ctx, const vgk_gssw_problem* problems, uint32_t n, ui
     P.walk_passes = walk2 && !P.fused ? 2 : 1;                          // (local alignments with a traceback: what walk_diag_one serves)
     if (P.walk_passes != 2 || P.tb_mode != TB_CODES) P.spec_fill = 0;
     set_refill_bound(P, ctx);
+    set_refill_walk(P);
     P.key3 = 0; P.row_off = 0;
     if (P.spec_fill) {                                                  // the first fill's column key maximum by v_pk_maximum3_f16 (gssw_device.hpp, K3)
         uint32_t longest = 0; bool xdrop = false;

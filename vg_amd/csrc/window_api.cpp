@@ -303,6 +303,7 @@ int vgk_pack_windows_impl(vgk_ctx* ctx, const vgk_dgraph* dg, const char* reads,
     P.walk_passes = walk2 ? 2 : 1;                                    // (windows that were made on the device are tails: X-drop)
     if (P.walk_passes != 2 || P.tb_mode != TB_CODES) P.spec_fill = 0;
     set_refill_bound(P, ctx);
+    set_refill_walk(P);
     P.key3 = 0; P.row_off = 0;
     if (P.spec_fill) {                                                  // (speculation only with the problems at hand on the host: walk2)
         uint32_t longest = 0; bool xdrop = false;
