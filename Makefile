@@ -96,3 +96,18 @@ readaln_san: tests/emu/read_alignments_san
 tests/emu/read_alignments_san: tests/emu/read_alignments_driver.cpp $(LIB_HDRS)
 	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -DRA_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 .PHONY: readaln readaln_san
+
+# test-only: vgk_haplo_create + vgk_gapless_extend on the emulated backend as a program of its own under the host sanitizers — the lane code of
+# gapless_device.hpp and its per-thread slabs on the limits the edge corpus of tests/test_gapless_definition.py sits on
+gapless_san: tests/emu/gapless_san
+SAN_FLAGS := -O1 -g -std=c++17 -Iinclude -Wall -DVGK_PK_CHECK -fsanitize=address,undefined -fno-sanitize-recover=undefined
+SAN_OBJS := $(patsubst vg_amd/csrc/%.cpp,tests/emu/san_obj/%.o,$(wildcard vg_amd/csrc/*.cpp)) tests/emu/san_obj/backend_emu.o tests/emu/san_obj/gapless_san_main.o
+tests/emu/san_obj/%.o: vg_amd/csrc/%.cpp $(LIB_HDRS)
+	@mkdir -p tests/emu/san_obj
+	$(CXX) $(SAN_FLAGS) -c $< -o $@
+tests/emu/san_obj/%.o: tests/emu/%.cpp $(LIB_HDRS)
+	@mkdir -p tests/emu/san_obj
+	$(CXX) $(SAN_FLAGS) -c $< -o $@
+tests/emu/gapless_san: $(SAN_OBJS)
+	$(CXX) -fsanitize=address,undefined -o $@ $(SAN_OBJS) -lpthread
+.PHONY: gapless_san

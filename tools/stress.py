@@ -58,6 +58,15 @@ for qa in (None, qualadj.qual_adj_tables()):
 # gapless
 total, full = test_gapless.compare_engines(None, range(seed * 1000, seed * 1000 + 150), n_reads=600)
 print("gapless: %d extensions over 90000 reads identical (%d full-length sets)" % (total, full))
+# ... and the engine's sets against the rule stated from the thread lists (tests/refgapless.py): every extension valid, every set within the set rules
+import refgapless
+checked = 0
+for s in range(seed * 1000, seed * 1000 + 10):
+    nodes, threads, problems = test_gapless.random_haplotype_case(np.random.default_rng(s), n_reads=200)
+    eng = capi.Engine(); hap = refgapless.Haplotypes(nodes, threads)
+    for p, (status, full_length, exts) in zip(problems, refgapless.sets_of(eng.gapless_extend(eng.haplo_index(nodes, threads), problems))):
+        checked += refgapless.check_set(hap, refgapless.mask(p["read"]), p, status, full_length, exts)
+print("gapless: %d extensions of 2000 reads meet the reference's validity and set rules" % checked)
 # WFA (incl. cyclic threads, custom error models) and the k-best pinned tracebacks
 import test_wfa
 import test_pinned_multi

@@ -349,7 +349,10 @@ static int gapless_run_and_fetch(vgk_ctx* ctx, GaplessParams& P, uint32_t n, uin
     { const int rc0 = ctx->finish_deferred(); if (rc0) return rc0; }         // (an earlier call's sets still on their way use the same staging)
     P.match = ctx->sc.matrix[0]; P.mismatch = -ctx->sc.matrix[1]; P.bonus = ctx->sc.full_length_bonus;
     // dense outputs: at most one extension per seed; nodes / mismatches sized generously and checked on the device
-    const uint64_t cap_e = n_seed + 1, cap_n = std::min<uint64_t>(n_seed * G_PATH, std::max<uint64_t>(n_seed * 16 + 1024, nodes_cap)) + 1,
+    // (with merged runs an extension of at most G_PATH MERGED nodes goes out in the original nodes its interval touches, which may be more: there
+    // the caller's room alone bounds the nodes)
+    const uint64_t path_bound = P.merge.on ? ~0ull : n_seed * G_PATH;
+    const uint64_t cap_e = n_seed + 1, cap_n = std::min<uint64_t>(path_bound, std::max<uint64_t>(n_seed * 16 + 1024, nodes_cap)) + 1,
                    cap_m = std::min<uint64_t>(n_seed * G_MISM, std::max<uint64_t>(n_seed * 8 + 1024, mism_cap)) + 1;
     P.flat_min_idle = G_FLAT_MIN_IDLE;
     if (const char* e = std::getenv("VGAMD_GAPLESS_MIN_IDLE")) P.flat_min_idle = (uint32_t)std::max(1, std::atoi(e));

@@ -592,11 +592,13 @@ VGK_HD uint32_t gx_overlap(const GIndex& h, const GExt& x, const GExt& y) {     
 }
 VGK_HD bool gs_eq(const GState& a, const GState& b) { return a.fn == b.fn && a.flo == b.flo && a.fhi == b.fhi && a.bn == b.bn && a.blo == b.blo && a.bhi == b.bhi; }
 VGK_HD bool gx_eq(const GExt& a, const GExt& b) { return a.r0 == b.r0 && a.r1 == b.r1 && gs_eq(a.state, b.state) && a.offset == b.offset; }
-VGK_HD bool gx_dup_less(const GExt& a, const GExt& b) {                                            // (:333-349)
+// (abn, afn | bbn, bfn: the states' nodes as the caller knows them — with merged runs the ORIGINAL first and last nodes, gx_orig_ends: two
+// extensions that end inside one merged node are ordered by the nodes they end on, and a reverse run numbers its nodes downwards)
+VGK_HD bool gx_dup_less(const GExt& a, const GExt& b, int32_t abn, int32_t afn, int32_t bbn, int32_t bfn) {      // (:333-349)
     if (a.r0 != b.r0) return a.r0 < b.r0;
     if (a.r1 != b.r1) return a.r1 < b.r1;
-    if (a.state.bn != b.state.bn) return a.state.bn < b.state.bn;
-    if (a.state.fn != b.state.fn) return a.state.fn < b.state.fn;
+    if (abn != bbn) return abn < bbn;
+    if (afn != bfn) return afn < bfn;
     if (a.state.blo != b.state.blo) return a.state.blo < b.state.blo;
     if (a.state.bhi != b.state.bhi) return a.state.bhi < b.state.bhi;
     if (a.state.flo != b.state.flo) return a.state.flo < b.state.flo;
@@ -611,8 +613,8 @@ VGK_HD bool gx_full_less(const GExt& a, const GExt& b) {                        
 template <class RESV, class Less> VGK_HD void gx_sort(const RESV& v, uint8_t* order, uint32_t n, Less less) {
     for (uint32_t i = 1; i < n; ++i) { const uint8_t x = order[i]; uint32_t j = i; while (j && less(v[x], v[order[j - 1]])) { order[j] = order[j - 1]; --j; } order[j] = x; }
 }
-template <class RESV> VGK_HD uint32_t gx_remove_duplicates(const RESV& v, uint8_t* order, uint32_t n) {                  // (:332-365)
-    gx_sort(v, order, n, [](const GExt& a, const GExt& b) { return gx_dup_less(a, b); });
+template <class RESV, class Less> VGK_HD uint32_t gx_remove_duplicates(const RESV& v, uint8_t* order, uint32_t n, Less less) {      // (:332-365)
+    gx_sort(v, order, n, less);
     uint32_t tail = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const GExt& e = v[order[i]];
@@ -901,7 +903,8 @@ VGK_HD int g_search_end(const GaplessParams& P, const ST& Q, const GSearch& s, G
 
 // merged runs: the ORIGINAL oriented nodes an extension's aligned interval touches, in path order -> their number; out (nullable): written there;
 // first_offset (nullable): in: the offset in the first merged node, out: the offset in the first original node
-VGK_HD uint32_t gx_expand(const GaplessParams& P, const GExt& e, uint32_t* out, uint32_t* first_offset) {
+// ends (nullable): [0] the first, [1] the last of them
+VGK_HD uint32_t gx_expand(const GaplessParams& P, const GExt& e, uint32_t* out, uint32_t* first_offset, uint32_t* ends = nullptr) {
     const GMerge& M = P.merge;
     uint32_t n = 0, left = e.r1 - e.r0, a = e.offset;
     for (uint32_t i = 0; i < e.path_len && left; ++i) {
@@ -917,6 +920,7 @@ VGK_HD uint32_t gx_expand(const GaplessParams& P, const GExt& e, uint32_t* out, 
             if (s0 >= b) break;
             if (n == 0 && first_offset) *first_offset = a - s0;
             if (out) out[n] = 2u * v + rev;
+            if (ends) { if (n == 0) ends[0] = 2u * v + rev; ends[1] = 2u * v + rev; }
             ++n;
         }
         left -= b - a; a = 0;
@@ -924,6 +928,12 @@ VGK_HD uint32_t gx_expand(const GaplessParams& P, const GExt& e, uint32_t* out, 
     return n;
 }
 
+// merged runs: the nodes of an extension's search state in ORIGINAL terms — what remove_duplicates orders by (:337-342)
+VGK_HD void gx_orig_ends(const GaplessParams& P, const GExt& e, int32_t& bn, int32_t& fn) {
+    uint32_t ends[2];
+    if (gx_expand(P, e, nullptr, nullptr, ends)) { bn = (int32_t)(ends[0] ^ 1u); fn = (int32_t)ends[1]; }
+    else { bn = e.state.bn; fn = e.state.fn; }                     // (an empty extension: dropped by the caller whatever its place)
+}
 // The rules over a read's winners (the second half of GaplessExtender::extend): RES(i) = the i-th USED winner, n_res of them, in seed
 // order; best_alignment as the seed loop left it.  `order` = n_res bytes of scratch for the permutation the rules sort.
 template <bool MG, class RESV>
@@ -955,15 +965,20 @@ VGK_HD void gapless_set_rules(const GaplessParams& P, uint32_t pi, const GProb& 
         for (uint32_t i = 0; i < n_out; ++i) { gx_find_mismatches(c, RES[order[i]], mm, overflow); mm_owner = order[i]; }      // counts, for the output sizes
         out.full_length = 1;
     } else {
-        n_out = gx_remove_duplicates(RES, order, n_res);
+        auto dup_less = [&P](const GExt& a, const GExt& b) {
+            int32_t abn = a.state.bn, afn = a.state.fn, bbn = b.state.bn, bfn = b.state.fn;
+            if (MG && P.merge.on && a.r0 == b.r0 && a.r1 == b.r1) { gx_orig_ends(P, a, abn, afn); gx_orig_ends(P, b, bbn, bfn); }
+            return gx_dup_less(a, b, abn, afn, bbn, bfn);
+        };
+        n_out = gx_remove_duplicates(RES, order, n_res, dup_less);
         bool trimmed = false;
         for (uint32_t i = 0; i < n_out && !overflow; ++i) {
             gx_find_mismatches(c, RES[order[i]], mm, overflow); mm_owner = order[i];
             if (!overflow && (pb.flags & VGK_GAPLESS_TRIM)) trimmed |= gx_trim(c, RES[order[i]], mm);
         }
-        if (trimmed) n_out = gx_remove_duplicates(RES, order, n_out);
+        if (trimmed) n_out = gx_remove_duplicates(RES, order, n_out, dup_less);
     }
-    if (overflow) { out.status = VGK_ETOOBIG; return; }
+    if (overflow) { out.status = VGK_ETOOBIG; out.full_length = 0; return; }      // (a declined read carries no set: not a full-length one either)
     // hand the set out (merged runs: in the ORIGINAL nodes the aligned interval touches — gx_expand)
     uint32_t nn = 0, nm = 0;
     for (uint32_t i = 0; i < n_out; ++i) { nn += (MG && P.merge.on) ? gx_expand(P, RES[order[i]], nullptr, nullptr) : RES[order[i]].path_len; nm += RES[order[i]].n_mism; }
