@@ -97,6 +97,16 @@ tests/emu/read_alignments_san: tests/emu/read_alignments_driver.cpp $(LIB_HDRS)
 	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -DRA_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 .PHONY: readaln readaln_san
 
+# test-only: the serial form of the device rules for a read's mapping quality — agglomerations, the scores' quality and the explored cap
+# (read_mapq_device.hpp: mq_region_one, mq_read_one) behind one C call each, and the same as a program of its own under the host sanitizers
+readmapq: tests/emu/libvgamd_readmapq.so
+tests/emu/libvgamd_readmapq.so: tests/emu/read_mapq_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -shared -o $@ $<
+readmapq_san: tests/emu/read_mapq_san
+tests/emu/read_mapq_san: tests/emu/read_mapq_driver.cpp $(LIB_HDRS)
+	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -DMQ_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+.PHONY: readmapq readmapq_san
+
 # test-only: vgk_haplo_create + vgk_gapless_extend on the emulated backend as a program of its own under the host sanitizers — the lane code of
 # gapless_device.hpp and its per-thread slabs on the limits the edge corpus of tests/test_gapless_definition.py sits on
 gapless_san: tests/emu/gapless_san

@@ -259,6 +259,62 @@ int vgk_read_alignments_limits(uint32_t out[4]);
 /* Device time (ms) of the last vgk_read_alignments call on this context: selection | count + prefix sums | emit */
 int vgk_read_alignments_last_ms(vgk_ctx* ctx, double ms[3]);
 
+/* ---- a read's mapping quality on the device: the alignments' scores and the explored-minimizer cap --------------------------------------------
+ * What both mapping routes close with (MinimizerMapper::map, src/minimizer_mapper.cpp:1143-1188; map_from_chains,
+ * src/minimizer_mapper_from_chains.cpp:957-1057): the mapping quality of the alignments' scores (MappingQualityCalculator's exact form), capped by
+ * faster_cap over the explored minimizers (:2946-3260, the Phred-scaled probability that sequencing errors created all of them), the escape bonus,
+ * round, clamp to 0 .. 60.  The rule is stated serially in vg_amd/csrc/read_mapq_device.hpp (mq_region_one, mq_read_one), which the kernels call.
+ *
+ * vgk_minimizer_regions: per minimizer of a list as vgk_minimizer_list / vgk_minimizer_find_seeds answer it (offset order per read; any list: no
+ * index is needed, hash = Thomas Wang's mix of the key) its agglomeration {start, length} in read bases: from the start of the first window the
+ * instance wins to the end of the last (window s = k-mers [s, s + w) = bases [s, s + w + k - 1); its minimizer is the leftmost smallest canonical
+ * hash among its valid k-mers; src/minimizer_mapper.hpp:565-600).  Only the list is read: an instance's windows follow from its two neighbours.
+ * VGK_EINVAL for the call: k or w outside what the index takes, offsets that do not ascend from 0, a minimizer that does not fit its read or whose
+ * read has no complete window, a list out of offset order; VGK_ETOOBIG beyond 2^32 - 16 minimizers.
+ *
+ * vgk_read_mapq: per read r
+ *   scores[score_off[r] .. score_off[r + 1])  the alignments' scores in the reference's `scores` order (the log-sum runs backwards over it), with
+ *   multiplicity (nullable; as long as scores) and unmapped[r] (nullable; non-zero: the first alignment has no mappings, mapping quality 0);
+ *   minimizers[minimizer_off[r] .. minimizer_off[r + 1]) with their regions and explored (one byte each, non-zero: the minimizer was explored);
+ *   read_off for the length; quality (nullable: the cap is +infinity, as faster_cap returns) holds read r's Phred bytes at read_off[r].
+ * A minimizer's forward_offset is its offset (the k-mer's first base), its length is the scheme's k — or, under VGK_READ_MAPQ_OWN_LENGTH, its own
+ * `reserved` field (the lists of the reference's unit tests hold minimizers of several lengths).
+ * Out, per read: mapq = clamp(round(min(bonus * explored_cap, uncapped)), 0, 60) with bonus = 2 where uncapped is INT32_MAX, else 1; uncapped = the
+ * scores' mapping quality after the reference's (int32_t) truncation (INT32_MAX: infinite; 0 for an unmapped read); explored_cap = the cap before the
+ * bonus (+infinity without qualities or under VGK_READ_MAPQ_NO_EXPLORED_CAP; -0.0 when nothing was explored, as in the reference).
+ * status VGK_EINVAL, with mapq 0, for a read on which the reference stops — a mapped read without scores, an explored minimizer of length 0,
+ * "minimizers seem impossible to disrupt" (a column's probability underflows to 0), "not sorted / stacked properly" (unreachable once the
+ * explored minimizers are sorted, kept as the reference keeps it) — or whose explored minimizer is longer than the 32 events the probability table holds
+ * or has an agglomeration that begins behind the read's last base (the reference would read qualities that are not there).
+ * For the call: VGK_EINVAL offsets that do not ascend from 0, unknown flags, a log_base or score_scale that is not finite and positive;
+ * VGK_ETOOBIG beyond 2^32 - 16 of anything, or 2^24 minimizers in one read.  Ties of (agglomeration end, start) among explored minimizers keep list order
+ * (the reference leaves them to std::sort; agglomerations as vgk_minimizer_regions makes them never tie). */
+typedef struct vgk_minimizer_region { uint32_t start, length; } vgk_minimizer_region;
+enum { VGK_READ_MAPQ_FIRST = 1,            /* compute_first_mapping_quality: the chain route's form (default: compute_max_mapping_quality) */
+       VGK_READ_MAPQ_NO_EXPLORED_CAP = 2,  /* use_explored_cap == false */
+       VGK_READ_MAPQ_OWN_LENGTH = 4 };     /* a minimizer's length is its `reserved` field */
+typedef struct vgk_read_mapq_scheme {
+    double   log_base;                    /* the scorer's, as MappingQualityCalculator takes it */
+    double   score_scale;                 /* mapq_score_scale (1.0: off) */
+    uint32_t score_window;                /* mapq_score_window (0: off) */
+    uint32_t k;
+    uint32_t flags;                       /* VGK_READ_MAPQ_* */
+    uint32_t reserved;
+} vgk_read_mapq_scheme;
+typedef struct vgk_read_mapq_result { int32_t mapq; int32_t status; double uncapped; double explored_cap; } vgk_read_mapq_result;      /* 24 B */
+int vgk_minimizer_regions(vgk_ctx* ctx, uint32_t k, uint32_t w, const uint64_t* read_off, uint32_t n, const uint64_t* minimizer_off,
+                          const vgk_read_minimizer* minimizers, vgk_minimizer_region* regions);
+int vgk_read_mapq(vgk_ctx* ctx, const vgk_read_mapq_scheme* scheme, uint32_t n, const uint64_t* score_off, const int32_t* scores, const double* multiplicity,
+                  const uint8_t* unmapped, const uint64_t* minimizer_off, const vgk_read_minimizer* minimizers, const vgk_minimizer_region* regions,
+                  const uint8_t* explored, const uint64_t* read_off, const uint8_t* quality, vgk_read_mapq_result* out /* [n] */);
+/* out[0] = explored minimizers of a read whose order and c[] table the sweep keeps in LDS (a lane per read; reads with more run in a second launch
+ * over a slab in HBM), out[1] = lanes per read in the sweep, out[2] = lanes per minimizer in vgk_minimizer_regions, out[3] = 0 (reserved) */
+int vgk_read_mapq_limits(uint32_t out[4]);
+/* Device time (ms) of the last vgk_minimizer_regions | vgk_read_mapq call on this context */
+int vgk_read_mapq_last_ms(vgk_ctx* ctx, double ms[2]);
+/* Reads of the last vgk_read_mapq call by where they ran: swept in LDS | swept over the slab | not swept (refused by the checks) */
+int vgk_read_mapq_last_launches(vgk_ctx* ctx, uint64_t reads[3]);
+
 /* ---- windows of the resident graph, of any read length: the wide route on the device ------------------------------------------------------
  * vgk_gssw_pack_windows (vgk.h) takes what the packed kernels take: at most 1024 DP rows, scores inside 11 bits; a longer window fails the whole
  * pack with VGK_ETOOLONG.  This one-call entry takes windows of any read length and scoring and answers every problem in its own status, as

@@ -211,6 +211,54 @@ def read_alignments_call(fn, head, reads, read_off, results, extensions, nodes, 
     return rc, out
 
 
+# vgk_minimizer_regions / vgk_read_mapq (include/vgk_engine.h): a read's mapping quality from its alignments' scores and its explored minimizers
+MINIMIZER_REGION_DT = np.dtype([("start", "<u4"), ("length", "<u4")])
+READ_MAPQ_RESULT_DT = np.dtype([("mapq", "<i4"), ("status", "<i4"), ("uncapped", "<f8"), ("explored_cap", "<f8")])
+assert MINIMIZER_REGION_DT.itemsize == 8 and READ_MAPQ_RESULT_DT.itemsize == 24
+READ_MAPQ_FIRST, READ_MAPQ_NO_EXPLORED_CAP, READ_MAPQ_OWN_LENGTH = 1, 2, 4
+INT32_MAX = 0x7fffffff
+
+
+class ReadMapqScheme(ctypes.Structure):         # vgk_read_mapq_scheme
+    _fields_ = [("log_base", ctypes.c_double), ("score_scale", ctypes.c_double), ("score_window", ctypes.c_uint32), ("k", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def minimizer_regions_call(fn, head, k, w, read_off, minimizer_off, minimizers, between=(), tail=()):
+    """one call with vgk_minimizer_regions' arguments (the engine's, the serial lane code's, the host shim's vgh_minimizer_regions): head / between / tail =
+    the ctypes values the function takes before `k` / behind `w` (the shim: the reads) / behind `regions` -> (rc, regions MINIMIZER_REGION_DT)"""
+    off = np.ascontiguousarray(read_off, dtype=np.uint64); moff = np.ascontiguousarray(minimizer_off, dtype=np.uint64); n = len(off) - 1
+    recs = np.ascontiguousarray(minimizers, dtype=READ_MINIMIZER_DT)
+    regions = np.zeros(max(len(recs), 1), dtype=MINIMIZER_REGION_DT)
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_uint32, ctypes.c_uint32] + [type(t) for t in between] + [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p] \
+        + [type(t) for t in tail]
+    rc = fn(*head, int(k), int(w), *between, off.ctypes.data, n, moff.ctypes.data, recs.ctypes.data if len(recs) else None, regions.ctypes.data, *tail)
+    return rc, regions[:len(recs)]
+
+
+def read_mapq_call(fn, head, scheme, score_off, scores, minimizer_off, minimizers, regions, explored, read_off, quality=None, multiplicity=None, unmapped=None, tail=()):
+    """one call with vgk_read_mapq's arguments (the engine's, the host shim's vgh_read_mapq, the serial lane code's): head / tail = the ctypes values the
+    function takes before `scheme` / behind `out`.  scheme: a ReadMapqScheme -> (rc, results READ_MAPQ_RESULT_DT)"""
+    soff = np.ascontiguousarray(score_off, dtype=np.uint64); moff = np.ascontiguousarray(minimizer_off, dtype=np.uint64); off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    n = len(off) - 1
+    sc = np.ascontiguousarray(scores, dtype=np.int32); recs = np.ascontiguousarray(minimizers, dtype=READ_MINIMIZER_DT); reg = np.ascontiguousarray(regions, dtype=MINIMIZER_REGION_DT)
+    ex = np.ascontiguousarray(explored, dtype=np.uint8)
+    assert len(reg) == len(recs) == len(ex) and len(soff) == len(moff) == n + 1
+    q = None if quality is None else np.ascontiguousarray(quality, dtype=np.uint8)
+    mult = None if multiplicity is None else np.ascontiguousarray(multiplicity, dtype=np.float64)
+    un = None if unmapped is None else np.ascontiguousarray(unmapped, dtype=np.uint8)
+    out = np.zeros(max(n, 1), dtype=READ_MAPQ_RESULT_DT)
+    if q is not None and not len(q):
+        q = np.zeros(1, dtype=np.uint8)                               # (given, though no read has a base: still "with qualities")
+    ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 11 + [type(t) for t in tail]
+    rc = fn(*head, ctypes.byref(scheme), n, soff.ctypes.data, ptr(sc), ptr(mult), ptr(un), moff.ctypes.data, ptr(recs), ptr(reg), ptr(ex), off.ctypes.data,
+            ptr(q), out.ctypes.data, *tail)
+    return rc, out[:n]
+
+
 MINIMIZER_REVERSE = 1
 # vgk_chain_stitch (include/vgk.h): pieces of a read's chain in, one composed alignment per read out
 CHAIN_PIECE_DT = np.dtype([("kind", "<u4"), ("link", "<u4"), ("node_offset", "<u4"), ("path_begin", "<u4"), ("path_len", "<u4"), ("edit_begin", "<u4"), ("n_edits", "<u4"), ("reserved", "<u4")])
@@ -879,6 +927,41 @@ class Engine:
         self.lib.vgk_read_alignments_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._check(self.lib.vgk_read_alignments_last_ms(self.h, ms), "vgk_read_alignments_last_ms")
         return tuple(float(x) for x in ms)
+
+    def minimizer_regions(self, k, w, read_off, minimizer_off, minimizers):
+        """vgk_minimizer_regions (include/vgk_engine.h): the agglomeration of every minimizer of a list as minimizer_list / minimizer_find_seeds answer it
+        -> MINIMIZER_REGION_DT per minimizer (start, length in read bases)"""
+        rc, regions = minimizer_regions_call(self.lib.vgk_minimizer_regions, (self.h,), k, w, read_off, minimizer_off, minimizers)
+        self._check(rc, "vgk_minimizer_regions")
+        return regions
+
+    def read_mapq(self, scheme, score_off, scores, minimizer_off, minimizers, regions, explored, read_off, quality=None, multiplicity=None, unmapped=None):
+        """vgk_read_mapq (include/vgk_engine.h): per read the mapping quality of its alignments' scores, capped by faster_cap over its explored minimizers.
+        scheme: a ReadMapqScheme -> READ_MAPQ_RESULT_DT per read (mapq, status, uncapped, explored_cap)"""
+        rc, out = read_mapq_call(self.lib.vgk_read_mapq, (self.h,), scheme, score_off, scores, minimizer_off, minimizers, regions, explored, read_off,
+                                 quality, multiplicity, unmapped)
+        self._check(rc, "vgk_read_mapq")
+        return out
+
+    def read_mapq_limits(self):
+        """-> (explored minimizers of a read swept in LDS, lanes per read, lanes per minimizer in minimizer_regions, 0)"""
+        out = (ctypes.c_uint32 * 4)()
+        self._check(self.lib.vgk_read_mapq_limits(out), "vgk_read_mapq_limits")
+        return tuple(int(x) for x in out)
+
+    def read_mapq_last_ms(self):
+        """device time of the last minimizer_regions | read_mapq call in ms"""
+        ms = (ctypes.c_double * 2)()
+        self.lib.vgk_read_mapq_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_read_mapq_last_ms(self.h, ms), "vgk_read_mapq_last_ms")
+        return tuple(float(x) for x in ms)
+
+    def read_mapq_last_launches(self):
+        """reads of the last read_mapq call: (swept in LDS, swept over the slab, refused by the checks)"""
+        reads = (ctypes.c_uint64 * 3)()
+        self.lib.vgk_read_mapq_last_launches.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_read_mapq_last_launches(self.h, reads), "vgk_read_mapq_last_launches")
+        return tuple(int(x) for x in reads)
 
     def minimizer_last_ms(self):
         self.lib.vgk_minimizer_last_ms.restype = ctypes.c_double; self.lib.vgk_minimizer_last_ms.argtypes = [ctypes.c_void_p]

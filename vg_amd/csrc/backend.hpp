@@ -25,6 +25,7 @@
 #include "chain_items_device.hpp"
 #include "extension_anchors_device.hpp"
 #include "read_alignments_device.hpp"
+#include "read_mapq_device.hpp"
 
 namespace vgk {
 
@@ -172,6 +173,10 @@ public:
     // one stage of vgk_read_alignments (read_alignments_device.hpp: RA_RUN_*), asynchronous on the main stream: a lane per read — the selection over the
     // reads p.ids[0 .. p.n), their working words in LDS or (p.work) in the slab; count and emit over all p.n_reads.  Optional
     virtual int   run_read_alignments(const RaParams& p, int what) { (void)p; (void)what; return VGK_EUNSUPPORTED; }
+    // vgk_minimizer_regions (read_mapq_device.hpp: mq_region_one), a lane per minimizer; vgk_read_mapq (mq_read_one), a lane per read of p.ids[0 .. p.n):
+    // order and c[] in LDS, or (p.work) in the slab at p.work_off.  Asynchronous on the main stream.  Optional
+    virtual int   run_minimizer_regions(const MqRegionParams& p) { (void)p; return VGK_EUNSUPPORTED; }
+    virtual int   run_read_mapq(const MqParams& p) { (void)p; return VGK_EUNSUPPORTED; }
     virtual int   run_tail(const TailParams& p, uint32_t threads) = 0;
     virtual int   run_tail_stage(const TStageParams& p, int what) = 0;     // one of the per-item stages of vgk_tail_stage (tail_device.hpp: TS_*)
     virtual int   run_rescue_requests(const RqParams& p, int what) = 0;    // one of the per-pair stages of vgk_rescue_requests (rescue_requests_device.hpp: RQ_*)

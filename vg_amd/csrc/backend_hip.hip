@@ -1331,6 +1331,22 @@ __global__ void __launch_bounds__(64) read_alignments_compose_kernel(const RaPar
     const uint32_t r = blockIdx.x * 64 + threadIdx.x;
     if (r < (what == RA_RUN_TAILS ? P.n_tails : P.n_reads)) ra_read_one(P, what, r, nullptr);
 }
+// ---- a read's mapping quality (read_mapq_device.hpp: mq_region_one and mq_read_one are the rules and the checkers).  Agglomerations: a lane per
+// minimizer.  The quality: a lane per read; the explored order and the c[] table lie in LDS, one slice per lane at an odd stride (no two lanes of a
+// wavefront start in one bank), for reads of up to MQ_LDS_EXPLORED explored minimizers; the others come in a launch of their own over slices of a slab.
+__global__ void __launch_bounds__(256) minimizer_regions_kernel(const MqRegionParams P) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < P.n_minimizers) mq_region_one(P, j);
+}
+__global__ void __launch_bounds__(64) read_mapq_kernel(const MqParams P) {
+    __shared__ uint32_t work[64 * MQ_LDS_STRIDE];
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < P.n) mq_read_one(P, P.ids[i], work + threadIdx.x * MQ_LDS_STRIDE);
+}
+__global__ void __launch_bounds__(64) read_mapq_slab_kernel(const MqParams P) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < P.n) mq_read_one(P, P.ids[i], P.work + P.work_off[i]);
+}
 __global__ void __launch_bounds__(64) chain_stitch_kernel(const CsParams P, const int what) {
     cs_one(P, what, blockIdx.x * 64 + threadIdx.x);
 }
@@ -2212,6 +2228,19 @@ public:
             if (!items) return VGK_OK;
             hipLaunchKernelGGL(read_alignments_compose_kernel, dim3((items + 63) / 64), dim3(64), 0, stream, p, what);
         } else return VGK_EINVAL;
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_minimizer_regions(const MqRegionParams& p) override {
+        hipSetDevice(dev);
+        if (!p.n_minimizers) return VGK_OK;
+        hipLaunchKernelGGL(minimizer_regions_kernel, dim3((uint32_t)((p.n_minimizers + 255) / 256)), dim3(256), 0, stream, p);
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_read_mapq(const MqParams& p) override {
+        hipSetDevice(dev);
+        if (!p.n) return VGK_OK;
+        if (p.work) hipLaunchKernelGGL(read_mapq_slab_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
+        else hipLaunchKernelGGL(read_mapq_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
     int run_minimizer_choose(const MzChooseParams& p, uint32_t blocks) override {

@@ -107,6 +107,9 @@ struct vgk_ctx {
     double chain_items_ms[3] = {0, 0, 0};   // last vgk_chain_items: legality + grouping | DP | traceback
     double extension_anchors_ms[3] = {0, 0, 0};   // last vgk_extension_anchors: seed anchors + diagonal sort | the extensions' seed lists | anchors
     double read_alignments_ms[3] = {0, 0, 0};   // last vgk_read_alignments: selection | count + prefix sums | emit
+    double read_mapq_ms[2] = {0, 0};   // last vgk_minimizer_regions | vgk_read_mapq
+    uint64_t read_mapq_reads[3] = {0, 0, 0};   // reads of the last vgk_read_mapq: swept in LDS | over the slab | refused by the checks
+    bool mapq_tables = false;      // phred_to_prob and prob_for_at_least_one are in READMAPQ_TABLES
     double tail_stage_ms[4] = {0, 0, 0, 0};   // last vgk_tail_stage: tails derived | forest | windows packed | kernels + totals
     double tail_ms = 0;            // device time of the last vgk_tail_forest call
     // the last batch of either call stays resident in the cached device buffers: what a re-run needs to launch it again

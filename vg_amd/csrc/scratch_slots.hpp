@@ -58,6 +58,11 @@ enum Slot : int {
     READALN_READS, READALN_READ_OFF, READALN_RES, READALN_EXT, READALN_NODES, READALN_MISM, READALN_TAILS, READALN_OPS, READALN_TAIL_OF, READALN_STATUS,
     READALN_IDS, READALN_WORK_OFF, READALN_WORK, READALN_CHOICE, READALN_ALN_COUNT, READALN_ALN_FIRST, READALN_MAP_COUNT, READALN_EDIT_COUNT,
     READALN_MAP_FIRST, READALN_EDIT_FIRST, READALN_OUT, READALN_MAPPINGS, READALN_EDITS, READALN_TOTALS,
+    // ---- read_mapq_api.cpp.  Never aliased: ctx->mapq_tables (the two probability tables go up once per context and stay in READMAPQ_TABLES).  The
+    // rest is per call: offsets of reads, scores and minimizers; the scores, multiplicities and unmapped bytes; the list, its regions, the explored
+    // bytes and the qualities; the checks' verdicts, the launches' reads, the large reads' slices and their slab; the 24-byte results
+    READMAPQ_TABLES, READMAPQ_READ_OFF, READMAPQ_SCORE_OFF, READMAPQ_MIN_OFF, READMAPQ_SCORES, READMAPQ_MULT, READMAPQ_UNMAPPED, READMAPQ_MINS, READMAPQ_REGIONS,
+    READMAPQ_EXPLORED, READMAPQ_QUAL, READMAPQ_STATUS, READMAPQ_IDS, READMAPQ_WORK_OFF, READMAPQ_WORK, READMAPQ_OUT,
     // ---- gssw_wide_window_api.cpp (nothing stays): the call's problems, reads and verdicts; a sub-batch's windows, per-node temporaries, sizes, their
     // sums, the order's keys; the results and ops packed for the way back.  The arenas the wide kernels read are the WIDE_* buffers (aliases below)
     WIDEWIN_PROBLEMS, WIDEWIN_READS, WIDEWIN_META, WIDEWIN_SUB, WIDEWIN_STORE, WIDEWIN_NODE_FLAGS, WIDEWIN_SLOT_AT, WIDEWIN_PRED_AT, WIDEWIN_WIN_SLOTS,

@@ -1390,3 +1390,89 @@ int vgh_extension_anchors(const uint32_t* oriented_node_length, uint64_t n_orien
     } catch (std::exception& e) { g_last_error = e.what(); return -1; }
 }
 }  // extern "C"
+
+// ---- a read's mapping quality (read_mapq.hpp): the checker and CPU baseline of vgk_minimizer_regions / vgk_read_mapq --------------------------------
+#include "read_mapq.hpp"
+#include <cmath>
+namespace {
+// reads [0, n) on `threads` host threads (0 = all); the first exception ends the call
+template <class F> void over_reads(uint32_t n, int threads, F one) {
+    unsigned T = threads > 0 ? (unsigned)threads : std::max(1u, std::thread::hardware_concurrency());
+    T = std::min<unsigned>(T, std::max<uint32_t>(1, n / 64));
+    std::atomic<uint32_t> next{0}; std::atomic<bool> failed{false}; std::string what; std::mutex what_mu;
+    auto work = [&]() {
+        try { for (uint32_t r = next.fetch_add(64); r < n && !failed; r = next.fetch_add(64)) for (uint32_t q = r; q < std::min(n, r + 64); ++q) one(q); }
+        catch (std::exception& e) { failed = true; std::lock_guard<std::mutex> lk(what_mu); what = e.what(); }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < T; ++t) pool.emplace_back(work);
+    work();
+    for (std::thread& t : pool) t.join();
+    if (failed) throw std::runtime_error(what);
+}
+}  // namespace
+extern "C" {
+// minimizer_regions for a batch, over vgk_minimizer_regions' arrays plus the reads themselves (the scan looks at every window); rc -1 for a list that
+// is not its read's
+int vgh_minimizer_regions(uint32_t k, uint32_t w, const char* reads, const uint64_t* read_off, uint32_t n, const uint64_t* minimizer_off,
+                          const vgk_read_minimizer* minimizers, vgk_minimizer_region* regions, int threads) {
+    try {
+        over_reads(n, threads, [&](uint32_t r) {
+            std::vector<MinimizerInstance> list;
+            for (uint64_t j = minimizer_off[r]; j < minimizer_off[r + 1]; ++j) { MinimizerInstance m; m.key = minimizers[j].key; m.offset = minimizers[j].offset; list.push_back(m); }
+            const std::vector<Agglomeration> a = minimizer_regions(std::string(reads + read_off[r], reads + read_off[r + 1]), k, w, list);
+            for (size_t i = 0; i < a.size(); ++i) regions[minimizer_off[r] + i] = vgk_minimizer_region{(uint32_t)a[i].start, (uint32_t)a[i].length};
+        });
+        return 0;
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+// read_mapq for a batch, over vgk_read_mapq's arrays and with its output; a read on which the reference stops: status VGK_EINVAL, the rest 0
+int vgh_read_mapq(const vgk_read_mapq_scheme* scheme, uint32_t n, const uint64_t* score_off, const int32_t* scores, const double* multiplicity, const uint8_t* unmapped,
+                  const uint64_t* minimizer_off, const vgk_read_minimizer* minimizers, const vgk_minimizer_region* regions, const uint8_t* explored,
+                  const uint64_t* read_off, const uint8_t* quality, vgk_read_mapq_result* out, int threads) {
+    try {
+        ReadMapqScheme s;
+        s.log_base = scheme->log_base; s.score_scale = scheme->score_scale; s.score_window = scheme->score_window;
+        s.first = (scheme->flags & VGK_READ_MAPQ_FIRST) != 0; s.use_explored_cap = !(scheme->flags & VGK_READ_MAPQ_NO_EXPLORED_CAP);
+        over_reads(n, threads, [&](uint32_t r) {
+            std::vector<double> sc(scores + score_off[r], scores + score_off[r + 1]), mult;
+            if (multiplicity) mult.assign(multiplicity + score_off[r], multiplicity + score_off[r + 1]);
+            std::vector<CapMinimizer> ms; std::vector<size_t> ex;
+            if (s.use_explored_cap) for (uint64_t j = minimizer_off[r]; j < minimizer_off[r + 1]; ++j) {
+                CapMinimizer m;
+                m.hash = minimizer_hash(minimizers[j].key); m.offset = minimizers[j].offset; m.is_reverse = false;      // (offset is the k-mer's first base always)
+                m.agglomeration_start = regions[j].start; m.agglomeration_length = regions[j].length;
+                m.length = (int32_t)std::min<uint32_t>((scheme->flags & VGK_READ_MAPQ_OWN_LENGTH) ? minimizers[j].reserved : scheme->k, 33u);
+                if (explored[j]) ex.push_back(ms.size());
+                ms.push_back(m);
+            }
+            const size_t L = (size_t)(read_off[r + 1] - read_off[r]);
+            const ReadMapq q = read_mapq(s, sc, mult, unmapped && unmapped[r], ms, ex, std::string(L, 'N'),
+                                         quality ? std::string((const char*)quality + read_off[r], (const char*)quality + read_off[r + 1]) : std::string());
+            out[r] = vgk_read_mapq_result{q.mapq, q.stopped ? VGK_EINVAL : VGK_OK, q.uncapped, q.explored_cap};
+        });
+        return 0;
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+// the shim's own pre-truncation mapping quality of scaled scores (MappingQualityCalculator::maximum_mapping_quality_exact over log_base * score, the
+// first-score form with first != 0) and the sum of exp(other - best) it rests on: what a comparison sets aside near an integer
+double vgh_read_mapq_direct(const double* scaled_scores, int n, const double* multiplicity, int first, double* sum_others) {
+    std::vector<double> s(scaled_scores, scaled_scores + n), m;
+    if (multiplicity) m.assign(multiplicity, multiplicity + n);
+    size_t idx = 0;
+    const double q = first ? MappingQualityCalculator::first_mapping_quality_exact(s, multiplicity ? &m : nullptr)
+                           : MappingQualityCalculator::maximum_mapping_quality_exact(s, &idx, multiplicity ? &m : nullptr);
+    if (sum_others) {
+        const double best = first ? (n ? s[0] : 0.0) : (n ? *std::max_element(s.begin(), s.end()) : 0.0);
+        bool skipped = false; double sum = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double mult = multiplicity && m[(size_t)i] > 1.0 ? m[(size_t)i] : 1.0;
+            if (!skipped && s[(size_t)i] == best && (!first || i == 0)) { skipped = true; sum += (mult - 1.0); continue; }
+            sum += mult * std::exp(s[(size_t)i] - best);
+        }
+        if (n == 1 && !(multiplicity && m[0] > 1.0)) sum += std::exp(0.0 - best);
+        *sum_others = sum;
+    }
+    return q;
+}
+}  // extern "C"

@@ -301,6 +301,44 @@ def read_alignments(eng, index, gs, stage, extension_score_threshold=1, max_loca
                                extension_score_threshold, max_local_extensions, window_length)
 
 
+def read_mapq_inputs(seeded, composed):
+    """What vgk_read_mapq takes of a read, from the seeding's answer (seed_long_reads(choice="device") / minimizer_find_seeds: minimizer_off, minimizers, take)
+    and the composed alignments of the reads (read_alignments / align_stage_device(composed=True)["composed"]): the scores of a read's alignments in their
+    order — BEST then SECOND, or the DIRECT ones; an alignment without mappings behind the first is no entry of the reference's `scores` —, the unmapped
+    byte (the first alignment has no mappings), and the explored bytes: on this pipeline a read's cluster is all its seeds, so a minimizer is explored
+    when it was taken and has hits.  -> dict(score_off, scores, unmapped, explored)"""
+    aln = composed["alignments"]; aln_off = np.ascontiguousarray(composed["aln_off"], dtype=np.int64); n = len(aln_off) - 1
+    first = np.zeros(len(aln), dtype=bool); first[aln_off[:-1][aln_off[:-1] < aln_off[1:]]] = True
+    counted = first | (aln["n_mappings"] > 0)
+    per_read = np.bincount(aln["read"][counted], minlength=n)[:n] if len(aln) else np.zeros(n, dtype=np.int64)
+    unmapped = np.ones(n, dtype=np.uint8)
+    lead = aln[aln_off[:-1][aln_off[:-1] < aln_off[1:]]]
+    unmapped[lead["read"]] = (lead["n_mappings"] == 0).astype(np.uint8)
+    recs = seeded["minimizers"]
+    explored = ((np.asarray(seeded["take"]) != 0) & (recs["hits"] > 0)).astype(np.uint8)
+    return dict(score_off=np.concatenate([[0], np.cumsum(per_read)]).astype(np.uint64), scores=aln["score"][counted].astype(np.int32), unmapped=unmapped, explored=explored)
+
+
+def read_mapq(eng, seeded, composed, read_off, quality, k, w, log_base, flags=0, score_scale=1.0, score_window=0, details=None):
+    """The mapping quality of every read on the device (vgk_minimizer_regions + vgk_read_mapq, include/vgk_engine.h): the agglomerations of the seeding's
+    minimizers, then the quality of the composed alignments' scores under the explored cap (read_mapq_inputs says which scores and which minimizers).
+    quality: the reads' Phred bytes laid out as the reads (None: no cap); log_base: the scorer's.  details: a dict that receives `per_read`
+    (READ_MAPQ_RESULT_DT), `regions` and the inputs.  -> int32 per ALIGNMENT, as gaf_lines(mapq=...) takes it: a read's first alignment carries the read's
+    mapping quality, any other 0"""
+    read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    regions = eng.minimizer_regions(k, w, read_off, seeded["minimizer_off"], seeded["minimizers"])
+    a = read_mapq_inputs(seeded, composed)
+    scheme = capi.ReadMapqScheme(float(log_base), float(score_scale), int(score_window), int(k), int(flags), 0)
+    per_read = eng.read_mapq(scheme, a["score_off"], a["scores"], seeded["minimizer_off"], seeded["minimizers"], regions, a["explored"], read_off, quality, None, a["unmapped"])
+    aln_off = np.ascontiguousarray(composed["aln_off"], dtype=np.int64)
+    mapq = np.zeros(len(composed["alignments"]), dtype=np.int32)
+    has = aln_off[:-1] < aln_off[1:]
+    mapq[aln_off[:-1][has]] = per_read["mapq"][has]
+    if details is not None:
+        details.update(a, per_read=per_read, regions=regions)
+    return mapq
+
+
 def read_alignments_gaf_view(reads, read_off, composed):
     """What gaf_lines takes, from read_alignments' result: one record per ALIGNMENT — its read's bases (seqs, seq_off), the headers' leading
     vgk_chain_result fields as CHAIN_RESULT_DT, and the scores.  -> (seqs, seq_off, results, score)"""

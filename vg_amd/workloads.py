@@ -1378,3 +1378,188 @@ class ReadAlignmentsWorkload:
 
     def call_arrays(self):
         return dict(reads=self.reads, read_off=self.read_off, results=self.res, extensions=self.ext, nodes=self.path_nodes, mismatches=self.mism, tails=self.tails, ops=self.ops)
+
+
+# ---- a read's mapping quality (vgk_minimizer_regions / vgk_read_mapq, include/vgk_engine.h) -------------------------------------------------------
+def wang_hash64(key):
+    """Thomas Wang's 64-bit mix over a uint64 array (mz_hash of vg_amd/csrc/minimizer_device.hpp)"""
+    key = np.asarray(key, dtype=np.uint64)
+    u = lambda x: np.uint64(x)
+    with np.errstate(over="ignore"):
+        key = (~key) + (key << u(21)); key = key ^ (key >> u(24)); key = (key + (key << u(3))) + (key << u(8)); key = key ^ (key >> u(14))
+        key = (key + (key << u(2))) + (key << u(4)); key = key ^ (key >> u(28)); key = key + (key << u(31))
+    return key
+
+
+def read_minimizers(reads, read_off, k, w):
+    """Every read's (k, w)-minimizers and their agglomerations, by looking at every window of every read: window s of a read is its k-mers [s, s + w), its
+    minimizer the leftmost smallest canonical hash among the k-mers of ACGT only; an instance's agglomeration runs from the start of the first window it
+    wins to the end of the last.  -> (minimizer_off [n + 1] uint64, records READ_MINIMIZER_DT in offset order, regions MINIMIZER_REGION_DT, winners:
+    per read the winning offset of every window, -1 for a window with no valid k-mer)"""
+    reads = np.ascontiguousarray(reads, dtype=np.uint8); off = np.ascontiguousarray(read_off, dtype=np.int64); n = len(off) - 1
+    N = len(reads)
+    none = (np.zeros(n + 1, dtype=np.uint64), np.zeros(0, dtype=capi.READ_MINIMIZER_DT), np.zeros(0, dtype=capi.MINIMIZER_REGION_DT), [np.zeros(0, dtype=np.int64) for _ in range(n)])
+    if N < k + w - 1:
+        return none
+    code = np.full(256, -1, dtype=np.int64)
+    for x, c in enumerate(b"ACGT"):
+        code[c] = x
+    c = code[reads]
+    n_kmers = N - k + 1
+    fwd = np.zeros(n_kmers, dtype=np.uint64); rev = np.zeros(n_kmers, dtype=np.uint64); bad = np.zeros(n_kmers, dtype=bool)
+    for i in range(k):
+        ci = c[i:i + n_kmers]
+        bad |= ci < 0
+        x = np.where(ci < 0, 0, ci).astype(np.uint64)
+        fwd |= x << np.uint64(2 * (k - 1 - i)); rev |= (np.uint64(3) - x) << np.uint64(2 * i)
+    read_of = np.searchsorted(off, np.arange(N), side="right") - 1
+    at = np.arange(n_kmers)
+    bad |= at + k > off[read_of[:n_kmers] + 1]                        # a k-mer that leaves its read
+    hf, hr = wang_hash64(fwd), wang_hash64(rev)
+    is_rev = hr < hf
+    h = np.where(is_rev, hr, hf); key = np.where(is_rev, rev, fwd)
+    n_windows = n_kmers - w + 1
+    view = np.lib.stride_tricks.sliding_window_view
+    # the leftmost smallest: order by (invalid, hash) — argmin of the pair, position breaking ties to the left
+    hv = view(np.where(bad, np.uint64(0xffffffffffffffff), h), w); bv = view(bad, w)
+    best = np.argmin(hv, axis=1)                                      # (first occurrence = leftmost; an invalid k-mer holds the largest value)
+    rows = np.arange(n_windows)
+    any_valid = ~bv.all(axis=1)
+    tie = bv[rows, best] & any_valid                                  # a valid k-mer whose hash IS the largest value, beaten to the left by an invalid one: look again
+    for s in np.nonzero(tie)[0]:
+        ok = np.nonzero(~bv[s])[0]
+        best[s] = ok[np.argmin(hv[s][ok])]
+    s_at = np.arange(n_windows)
+    real = s_at + w + k - 1 <= off[read_of[:n_windows] + 1]           # a window inside one read
+    winner = np.where(any_valid, s_at + best, -1)
+    winners = []
+    for r in range(n):
+        lo, L = int(off[r]), int(off[r + 1] - off[r])
+        nw = L - k - w + 2
+        winners.append(np.where(winner[lo:lo + nw] >= 0, winner[lo:lo + nw] - lo, -1) if nw > 0 else np.zeros(0, dtype=np.int64))
+    sel = np.nonzero(real & any_valid)[0]
+    g = winner[sel]                                                   # global offsets of the winners, window by window: never decreasing within a read
+    inst, first = np.unique(g, return_index=True)
+    last = len(g) - 1 - np.unique(g[::-1], return_index=True)[1]
+    recs = np.zeros(len(inst), dtype=capi.READ_MINIMIZER_DT); regions = np.zeros(len(inst), dtype=capi.MINIMIZER_REGION_DT)
+    r_of = read_of[inst]
+    recs["key"] = key[inst]; recs["offset"] = inst - off[r_of]; recs["flags"] = is_rev[inst].astype(np.uint32)
+    regions["start"] = sel[first] - off[r_of]; regions["length"] = sel[last] + w + k - 1 - sel[first]
+    moff = np.concatenate([[0], np.cumsum(np.bincount(r_of, minlength=n))]).astype(np.uint64)
+    return moff, recs, regions, winners
+
+
+class ReadMapqWorkload:
+    """Reads with their alignments' scores, minimizer lists, agglomerations, explored bytes and base qualities for vgk_read_mapq (include/vgk_engine.h):
+    n_short reads of 20-250 bases and n_long of 4-8 kbp over ACGT with a few N runs, their real (k, w)-minimizers and agglomerations (read_minimizers),
+    a random part of them explored — and reads planted for what the rule must reach: none explored, one alignment, equal top scores, a gap that makes the
+    quality infinite, a first score that is not the largest, multiplicities above 1, quality bytes 0 and >= 93, the unmapped byte, and the reads on which the
+    reference stops (stops(variant): read -> why), each a read of its own.  `variants` are the schemes the corpus is run under; arrays(variant) gives a call's arguments."""
+
+    def __init__(self, n_short=4000, n_long=16, seed=0, k=29, w=11, log_base=1.3862943611198906, lds_limit=64):
+        rng = np.random.default_rng(seed)
+        self.k, self.w, self.log_base = k, w, float(log_base)
+        lengths = np.concatenate([rng.integers(20, 251, n_short), rng.integers(4000, 8001, n_long)]).astype(np.int64)
+        lengths[:4] = (k + w - 2, k + w - 1, k + w, 250)
+        n_real = len(lengths)
+        special = ["no scores", "own length 0", "own length 33", "impossible to disrupt", "region behind the read", "exactly the LDS limit", "one beyond the LDS limit"]
+        lengths = np.concatenate([lengths, np.full(len(special), 400)])
+        self.n = n = len(lengths)
+        self.read_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64)
+        reads = ACGT[rng.integers(0, 4, int(lengths.sum()))]
+        for r in rng.integers(0, n_real, n_real // 10):                # N runs, shorter and longer than a window
+            a = int(self.read_off[r]) + int(rng.integers(0, lengths[r])); reads[a:min(a + int(rng.integers(1, 2 * (k + w))), int(self.read_off[r + 1]))] = ord("N")
+        self.reads = reads
+        moff, recs, regions, _ = read_minimizers(reads[:int(self.read_off[n_real])], self.read_off[:n_real + 1], k, w)
+        recs["reserved"] = k                                          # (the length, for the scheme that reads it there)
+        explored = (rng.random(len(recs)) < 0.7).astype(np.uint8)
+        nothing = rng.random(n_real) < 0.05                           # reads with no explored minimizer
+        explored[np.repeat(nothing, np.diff(moff.astype(np.int64)))] = 0
+        # ---- the planted lists: minimizers whose hash lies in bucket 0, agglomerations of their own
+        keys = rng.integers(0, 1 << 58, 80000).astype(np.uint64)
+        keys = np.unique(keys[(wang_hash64(keys) >> np.uint64(56)) == 0])
+        lists, regs, expl = [recs], [regions], [explored]
+        counts = list(np.diff(moff.astype(np.int64)))
+        self.stop_kinds = {}
+        limit = int(lds_limit)
+        for j, what in enumerate(special):
+            r = n_real + j
+            m = {"impossible to disrupt": 130, "exactly the LDS limit": limit, "one beyond the LDS limit": limit + 1}.get(what, 6)
+            rec = np.zeros(m, dtype=capi.READ_MINIMIZER_DT); reg = np.zeros(m, dtype=capi.MINIMIZER_REGION_DT)
+            rec["key"] = keys[:m]; rec["reserved"] = k
+            if what == "impossible to disrupt":                        # 130 agglomerations that begin at base 5, a quality of 255 there: 10^-25.5 x 0.00195^130 is 0
+                rec["offset"] = 300; reg["start"] = 5; reg["length"] = 1 + np.arange(m)
+            else:                                                      # a staircase: 3 bases apart, 45 long
+                rec["offset"] = 8 + 3 * np.arange(m); reg["start"] = 3 * np.arange(m); reg["length"] = 45
+            if what == "own length 0":
+                rec["reserved"][2] = 0
+            if what == "own length 33":
+                rec["reserved"][3] = 33
+            if what == "region behind the read":
+                reg["start"][m - 1] = 401
+            lists.append(rec); regs.append(reg); expl.append(np.ones(m, dtype=np.uint8)); counts.append(m)
+            if what in ("no scores", "impossible to disrupt", "region behind the read", "own length 0", "own length 33"):
+                self.stop_kinds[r] = what
+        self.mins = np.concatenate(lists); self.regions = np.concatenate(regs); self.explored = np.concatenate(expl)
+        self.min_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+        # ---- qualities: Illumina-like, with the extremes planted
+        qual = rng.integers(2, 42, len(reads)).astype(np.uint8)
+        some = rng.random(len(reads)) < 0.01
+        qual[some] = rng.choice(np.array([0, 93, 94, 200, 255], dtype=np.uint8), int(some.sum()))
+        qual[int(self.read_off[n_real + special.index("impossible to disrupt")]) + 5] = 255
+        self.qual = qual
+        # ---- scores, in the reference's order: mostly the best first
+        n_scores = rng.integers(1, 6, n); kind = rng.integers(0, 8, n)
+        scores, mult = [], []
+        for r in range(n):
+            top = int(rng.integers(15, int(lengths[r]) + 6))
+            if r == n_real:                                            # "no scores"
+                n_scores[r] = 0; continue
+            if kind[r] == 0:
+                s = [top]                                              # one alignment: the null-alignment term
+            elif kind[r] == 1:
+                s = [top, top] + [top - int(x) for x in rng.integers(0, 30, n_scores[r] - 1)]      # equal top scores
+            elif kind[r] == 2:
+                s = [top + 300] + [top - int(x) for x in rng.integers(0, 30, n_scores[r])]         # a gap that makes the quality infinite
+            elif kind[r] == 3:
+                s = [top - int(rng.integers(1, 4)), top] + [top - int(x) for x in rng.integers(0, 30, n_scores[r] - 1)]      # the first is not the largest (by little: its quality is small, not 0)
+            else:
+                s = [top] + [top - int(x) for x in rng.integers(1, 14, n_scores[r])]
+            n_scores[r] = len(s); scores += s
+            mult += [float(x) for x in np.where(rng.random(len(s)) < 0.2, rng.integers(2, 6, len(s)), 1)]
+        self.scores = np.array(scores, dtype=np.int32); self.mult = np.array(mult, dtype=np.float64)
+        self.score_off = np.concatenate([[0], np.cumsum(n_scores)]).astype(np.uint64)
+        self.unmapped = (rng.random(n) < 0.02).astype(np.uint8)
+        self.unmapped[n_real:] = 0
+        self.special = {what: n_real + j for j, what in enumerate(special)}
+        self.variants = [dict(name="short-read route"), dict(name="no qualities", quality=False),
+                         dict(name="chain route", flags=capi.READ_MAPQ_FIRST, multiplicity=True, score_scale=0.25, score_window=150),
+                         dict(name="chain route, no cap", flags=capi.READ_MAPQ_FIRST | capi.READ_MAPQ_NO_EXPLORED_CAP, multiplicity=True),
+                         dict(name="lengths of their own", flags=capi.READ_MAPQ_OWN_LENGTH, multiplicity=True)]
+
+    def stops(self, variant):
+        """the reads that must answer VGK_EINVAL under `variant`: read -> why"""
+        flags = int(variant.get("flags", 0)); swept = variant.get("quality", True) and not flags & capi.READ_MAPQ_NO_EXPLORED_CAP
+        return {r: what for r, what in self.stop_kinds.items()
+                if what == "no scores" or (swept and (what in ("impossible to disrupt", "region behind the read") or flags & capi.READ_MAPQ_OWN_LENGTH))}
+
+    def scheme(self, variant):
+        return capi.ReadMapqScheme(self.log_base, float(variant.get("score_scale", 1.0)), int(variant.get("score_window", 0)), int(variant.get("k", self.k)), int(variant.get("flags", 0)), 0)
+
+    def arrays(self, variant, reads=None):
+        """the arguments of capi.read_mapq_call behind `scheme`, for all reads or the reads `reads` (ascending)"""
+        a = dict(score_off=self.score_off, scores=self.scores, minimizer_off=self.min_off, minimizers=self.mins, regions=self.regions, explored=self.explored, read_off=self.read_off,
+                 quality=self.qual if variant.get("quality", True) else None, multiplicity=self.mult if variant.get("multiplicity") else None, unmapped=self.unmapped)
+        if reads is None:
+            return a
+        reads = np.asarray(reads, dtype=np.int64)
+
+        def pick(off, *arrs):
+            off = off.astype(np.int64); size = off[reads + 1] - off[reads]
+            idx = np.repeat(off[reads], size) + (np.arange(int(size.sum())) - np.repeat(np.cumsum(size) - size, size))
+            return (np.concatenate([[0], np.cumsum(size)]).astype(np.uint64),) + tuple(None if x is None else x[idx] for x in arrs)
+        a["score_off"], a["scores"], a["multiplicity"] = pick(self.score_off, a["scores"], a["multiplicity"])
+        a["minimizer_off"], a["minimizers"], a["regions"], a["explored"] = pick(self.min_off, a["minimizers"], a["regions"], a["explored"])
+        a["read_off"], a["quality"] = pick(self.read_off, a["quality"])
+        a["unmapped"] = self.unmapped[reads]
+        return a
