@@ -107,6 +107,17 @@ tests/emu/read_mapq_san: tests/emu/read_mapq_driver.cpp $(LIB_HDRS)
 	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -DMQ_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 .PHONY: readmapq readmapq_san
 
+# test-only: the serial form of the device rule for a pair's mapping qualities — pair scores, their order, the shared caps (pair_mapq_device.hpp:
+# pm_candidate_score, pm_pair_one; the mates' caps by read_mapq_device.hpp's mq_cap_one) behind one C call, and the same as a program of its own under
+# the host sanitizers
+pairmapq: tests/emu/libvgamd_pairmapq.so
+tests/emu/libvgamd_pairmapq.so: tests/emu/pair_mapq_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -shared -o $@ $<
+pairmapq_san: tests/emu/pair_mapq_san
+tests/emu/pair_mapq_san: tests/emu/pair_mapq_driver.cpp $(LIB_HDRS)
+	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -DPM_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+.PHONY: pairmapq pairmapq_san
+
 # test-only: vgk_haplo_create + vgk_gapless_extend on the emulated backend as a program of its own under the host sanitizers — the lane code of
 # gapless_device.hpp and its per-thread slabs on the limits the edge corpus of tests/test_gapless_definition.py sits on
 gapless_san: tests/emu/gapless_san

@@ -315,6 +315,89 @@ int vgk_read_mapq_last_ms(vgk_ctx* ctx, double ms[2]);
 /* Reads of the last vgk_read_mapq call by where they ran: swept in LDS | swept over the slab | not swept (refused by the checks) */
 int vgk_read_mapq_last_launches(vgk_ctx* ctx, uint64_t reads[3]);
 
+/* ---- a pair's mapping qualities on the device: pair scores, their order, the caps both mates share ---------------------------------------------
+ * What MinimizerMapper::map_paired closes with (src/minimizer_mapper.cpp:2476-2765; score_alignment_pair :6017-6028): the score of every
+ * candidate pairing, the score order with the max_multimaps cut, the multiplicities of rescued pairs, the pair's uncapped quality, the
+ * fragment-cluster cap, the two mates' explored caps summed, the unpaired cap, the halving for unreachable mates, and
+ * max(min(capped, 120) / 2, 0) truncated to the integer both mates carry.  Arithmetic on small per-pair lists: no distance index, no zip code, no
+ * graph.  The rule is stated serially in vg_amd/csrc/pair_mapq_device.hpp (pm_candidate_score, pm_pair_one), which the kernels call.
+ *
+ * Pair p is reads 2 p and 2 p + 1.  Per pair:
+ *   candidates[cand_off[p] .. cand_off[p + 1])  the entries of the reference's paired_alignments in creation order: the mates' alignment scores;
+ *     distance = what distance_between returned (INT64_MAX: unreachable; an UNPAIRED candidate counts as INT64_MAX whatever it holds); aln[r] = the
+ *     number of mate r's alignment among the pair's alignments of that mate (equal number = the same alignment; only the score groups read it);
+ *     better_cluster_count; type = the reference's PairType; aligned: bit r is set when mate r's alignment has mappings.
+ *   counts[p]  unpaired_count and rescued_count per mate.
+ *   unpaired_scores[unpaired_off[2 p + r] .. unpaired_off[2 p + r + 1])  mate r's unpaired alignments' scores (either pointer NULL: empty
+ *     everywhere); read only when the winner's type is UNPAIRED.
+ *   explored caps: given_cap[2 n] (for instance explored_cap of an earlier vgk_read_mapq) — or, when given_cap is NULL, vgk_read_mapq's minimizer
+ *     arguments for the 2 n reads: the call then runs that entry's sweep for both mates on the device and the caps stay in HBM for the pair kernels.
+ *     VGK_PAIR_MAPQ_NO_EXPLORED_CAP, or given_cap and quality both NULL: +infinity.
+ * The rule, in order.  (1) A candidate's pair score: for a rescued type whose rescued mate is not aligned, (double) the mapped mate's score
+ * (:2386-2391); otherwise score_alignment_pair: dev = distance - mean, ll = (-dev * dev / (2.0 * sd * sd)) / log_base,
+ * max(score0 + score1 + ll, min(score0, score1)), the integer sum first.  (2) Order: pair score descending (process_until_threshold_a with
+ * threshold 0, src/minimizer_mapper.hpp:1580-1659); equal scores stay in candidate order (the reference shuffles them with the read's generator:
+ * not pinned here); the first min(C, max_multimaps) are the mappings, all C scores in this order feed the quality.  (3) Multiplicities
+ * (:2660-2685): est[r] = unpaired_count[r] > 0 ? unpaired_count[r] / min(rescued_count[r], max_rescue_attempts) : 1.0; 1 for PAIRED and UNPAIRED,
+ * est[0] for RESCUED_FROM_FIRST, est[1] for RESCUED_FROM_SECOND; used only when no candidate is PAIRED.  (4) uncapped = 0 when the first ordered
+ * score is 0, else compute_max_mapping_quality (exact form, int32 truncation) over log_base * score.  (5) fragment_cluster_cap =
+ * -10 log10(1 - 1 / n) for the winner's better_cluster_count n > 1, else +infinity.  (6) Score groups (:2524-2546, :2704; annotation only, never
+ * applied): when the pair has a PAIRED candidate, group r = the winner's score, then — if the winner is PAIRED — the scores of the other PAIRED
+ * candidates with the winner's aln[r], in candidate order; score_group[r] = compute_max_mapping_quality of it (INT32_MAX for an empty group).
+ * (7) Per mate r (:2727-2765): bonus = 2 when uncapped is INT32_MAX, else 1; cap = min(fragment_cluster_cap, (explored_cap[0] + explored_cap[1]) *
+ * bonus), for an UNPAIRED winner also min with compute_max_mapping_quality(unpaired_scores[r]); capped = min(cap, uncapped), halved when the
+ * winner's distance is INT64_MAX; mapq[r] = (int32_t) max(min(capped, 120.0) / 2.0, 0.0), and 0 when the winner's mate r is not aligned.
+ * (8) A pair without candidates: both qualities 0, n_chosen 0, fragment_cluster_cap and score_group +infinity / INT32_MAX as above.
+ * Out, per pair: the 80-byte result (applied_cap[r] = the cap of step 7); per candidate pair_score (candidate order; a candidate's own, whatever
+ * becomes of its pair; 0 for a type above 3) and order (the candidate numbers within the pair in score order, laid out on cand_off; candidate
+ * order for a refused pair).
+ * Per pair VGK_EINVAL with everything else 0 (the call goes on): a type above 3; a rescued-type candidate when min(rescued_count,
+ * max_rescue_attempts) of its side is 0; an unaligned rescued mate with a finite distance; either mate stopped by the sweep (vgk_read_mapq's
+ * per-read refusals, less the one about scores).  For the call: VGK_EINVAL offsets that do not ascend from 0, unknown flags, log_base or
+ * fragment_sd not finite and positive, fragment_mean not finite; VGK_ETOOBIG beyond 2^32 - 16 of anything (2 n reads included).
+ * Out of scope: identify_supplementary_alignments; the max_rescue_attempts == 0 early return with quality 1 (:2238-2287); deriving
+ * better_cluster_count (:1653-1690) and distance_between, which are inputs; the proper-pair annotation. */
+enum { VGK_PAIR_PAIRED = 0, VGK_PAIR_UNPAIRED = 1, VGK_PAIR_RESCUED_FROM_FIRST = 2, VGK_PAIR_RESCUED_FROM_SECOND = 3 };
+enum { VGK_PAIR_MAPQ_NO_EXPLORED_CAP = 1 };
+typedef struct vgk_pair_candidate {
+    int32_t  score[2];
+    int64_t  distance;
+    uint32_t aln[2];
+    uint32_t better_cluster_count;
+    uint8_t  type;                        /* VGK_PAIR_* */
+    uint8_t  aligned;                     /* bit r: mate r's alignment has mappings */
+    uint16_t reserved;
+} vgk_pair_candidate;                     /* 32 B */
+typedef struct vgk_pair_counts { uint32_t unpaired_count[2], rescued_count[2]; } vgk_pair_counts;
+typedef struct vgk_pair_mapq_scheme {
+    double   log_base;                    /* the scorer's */
+    double   fragment_mean, fragment_sd;  /* fragment_length_distr */
+    uint32_t max_multimaps, max_rescue_attempts;
+    uint32_t k;                           /* the minimizers' length, for the sweep */
+    uint32_t flags;                       /* VGK_PAIR_MAPQ_* */
+} vgk_pair_mapq_scheme;
+typedef struct vgk_pair_mapq_result {
+    int32_t  mapq[2];
+    int32_t  status;
+    uint32_t n_chosen;                    /* min(candidates, max_multimaps) */
+    double   uncapped, fragment_cluster_cap, explored_cap[2], score_group[2], applied_cap[2];
+} vgk_pair_mapq_result;                   /* 80 B */
+int vgk_pair_mapq(vgk_ctx* ctx, const vgk_pair_mapq_scheme* scheme, uint32_t n /* pairs */, const uint64_t* cand_off, const vgk_pair_candidate* candidates,
+                  const vgk_pair_counts* counts, const uint64_t* unpaired_off /* [2 n + 1] */, const int32_t* unpaired_scores, const double* given_cap /* [2 n] */,
+                  const uint64_t* minimizer_off, const vgk_read_minimizer* minimizers, const vgk_minimizer_region* regions, const uint8_t* explored,
+                  const uint64_t* read_off, const uint8_t* quality, vgk_pair_mapq_result* out /* [n] */, double* pair_score, uint32_t* order);
+/* out[0] = candidates of a pair whose order and ordered scores the pair kernel keeps in LDS (a lane per pair; pairs with more run in a second launch
+ * over a slab in HBM), out[1] = lanes per pair, out[2] = lanes per candidate in the score kernel, out[3] = 0 (reserved) */
+int vgk_pair_mapq_limits(uint32_t out[4]);
+/* Device time (ms) of the last vgk_pair_mapq call on this context: the mates' sweep (0 with given caps) | the score and pair kernels */
+int vgk_pair_mapq_last_ms(vgk_ctx* ctx, double ms[2]);
+/* Pairs of the last vgk_pair_mapq call by where they ran: in LDS | over the slab | refused by the call's own checks (a stopped mate is found on
+ * the device and counts where its pair ran) */
+int vgk_pair_mapq_last_launches(vgk_ctx* ctx, uint64_t pairs[3]);
+/* Kernels the last vgk_pair_mapq call launched, counted where they are launched: the mates' sweep (0 with given caps; 2 when some read went over
+ * the slab) | the score kernel and the pair kernels (a launch list that is empty launches nothing) */
+int vgk_pair_mapq_last_kernel_launches(vgk_ctx* ctx, uint32_t launches[2]);
+
 /* ---- windows of the resident graph, of any read length: the wide route on the device ------------------------------------------------------
  * vgk_gssw_pack_windows (vgk.h) takes what the packed kernels take: at most 1024 DP rows, scores inside 11 bits; a longer window fails the whole
  * pack with VGK_ETOOLONG.  This one-call entry takes windows of any read length and scoring and answers every problem in its own status, as

@@ -259,6 +259,48 @@ def read_mapq_call(fn, head, scheme, score_off, scores, minimizer_off, minimizer
     return rc, out[:n]
 
 
+# vgk_pair_mapq (include/vgk_engine.h): a pair's mapping qualities from its candidate pairings and its mates' explored caps
+PAIR_CANDIDATE_DT = np.dtype([("score", "<i4", (2,)), ("distance", "<i8"), ("aln", "<u4", (2,)), ("better_cluster_count", "<u4"), ("type", "u1"), ("aligned", "u1"), ("reserved", "<u2")])
+PAIR_COUNTS_DT = np.dtype([("unpaired_count", "<u4", (2,)), ("rescued_count", "<u4", (2,))])
+PAIR_MAPQ_RESULT_DT = np.dtype([("mapq", "<i4", (2,)), ("status", "<i4"), ("n_chosen", "<u4"), ("uncapped", "<f8"), ("fragment_cluster_cap", "<f8"), ("explored_cap", "<f8", (2,)),
+                                ("score_group", "<f8", (2,)), ("applied_cap", "<f8", (2,))])
+assert PAIR_CANDIDATE_DT.itemsize == 32 and PAIR_COUNTS_DT.itemsize == 16 and PAIR_MAPQ_RESULT_DT.itemsize == 80
+PAIR_PAIRED, PAIR_UNPAIRED, PAIR_RESCUED_FROM_FIRST, PAIR_RESCUED_FROM_SECOND = 0, 1, 2, 3
+PAIR_MAPQ_NO_EXPLORED_CAP = 1
+INT64_MAX = 0x7fffffffffffffff
+
+
+class PairMapqScheme(ctypes.Structure):         # vgk_pair_mapq_scheme
+    _fields_ = [("log_base", ctypes.c_double), ("fragment_mean", ctypes.c_double), ("fragment_sd", ctypes.c_double), ("max_multimaps", ctypes.c_uint32),
+                ("max_rescue_attempts", ctypes.c_uint32), ("k", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+def pair_mapq_call(fn, head, scheme, cand_off, candidates, counts, unpaired_off=None, unpaired_scores=None, given_cap=None, minimizer_off=None, minimizers=None, regions=None,
+                   explored=None, read_off=None, quality=None, tail=()):
+    """one call with vgk_pair_mapq's arguments (the engine's, the host shim's vgh_pair_mapq, the serial lane code's): head / tail = the ctypes values the
+    function takes before `scheme` / behind `order`.  scheme: a PairMapqScheme -> (rc, results PAIR_MAPQ_RESULT_DT, pair_score float64 per candidate, order
+    uint32 per candidate)"""
+    coff = np.ascontiguousarray(cand_off, dtype=np.uint64); n = len(coff) - 1
+    cands = np.ascontiguousarray(candidates, dtype=PAIR_CANDIDATE_DT); cnt = np.ascontiguousarray(counts, dtype=PAIR_COUNTS_DT)
+    assert len(cnt) == n and int(coff[-1]) == len(cands)
+    opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+    uoff, usc, caps = opt(unpaired_off, np.uint64), opt(unpaired_scores, np.int32), opt(given_cap, np.float64)
+    moff, recs, reg, ex = opt(minimizer_off, np.uint64), opt(minimizers, READ_MINIMIZER_DT), opt(regions, MINIMIZER_REGION_DT), opt(explored, np.uint8)
+    off, q = opt(read_off, np.uint64), opt(quality, np.uint8)
+    assert (uoff is None or len(uoff) == 2 * n + 1) and (caps is None or len(caps) == 2 * n) and (moff is None or len(moff) == 2 * n + 1) and (off is None or len(off) == 2 * n + 1)
+    if usc is not None and not len(usc):
+        usc = np.zeros(1, dtype=np.int32)                             # (given, though no mate has one)
+    if q is not None and not len(q):
+        q = np.zeros(1, dtype=np.uint8)
+    out = np.zeros(max(n, 1), dtype=PAIR_MAPQ_RESULT_DT); pair_score = np.zeros(max(len(cands), 1), dtype=np.float64); order = np.zeros(max(len(cands), 1), dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None and len(a) else None
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 15 + [type(t) for t in tail]
+    rc = fn(*head, ctypes.byref(scheme), n, coff.ctypes.data, ptr(cands), ptr(cnt), ptr(uoff), ptr(usc), ptr(caps), ptr(moff), ptr(recs), ptr(reg), ptr(ex), ptr(off), ptr(q),
+            out.ctypes.data, pair_score.ctypes.data, order.ctypes.data, *tail)
+    return rc, out[:n], pair_score[:len(cands)], order[:len(cands)]
+
+
 MINIMIZER_REVERSE = 1
 # vgk_chain_stitch (include/vgk.h): pieces of a read's chain in, one composed alignment per read out
 CHAIN_PIECE_DT = np.dtype([("kind", "<u4"), ("link", "<u4"), ("node_offset", "<u4"), ("path_begin", "<u4"), ("path_len", "<u4"), ("edit_begin", "<u4"), ("n_edits", "<u4"), ("reserved", "<u4")])
@@ -962,6 +1004,41 @@ class Engine:
         self.lib.vgk_read_mapq_last_launches.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._check(self.lib.vgk_read_mapq_last_launches(self.h, reads), "vgk_read_mapq_last_launches")
         return tuple(int(x) for x in reads)
+
+    def pair_mapq(self, scheme, cand_off, candidates, counts, **rest):
+        """vgk_pair_mapq (include/vgk_engine.h): per pair both mates' mapping qualities from its candidate pairings — pair scores, their order, the caps both
+        mates share.  scheme: a PairMapqScheme; rest: pair_mapq_call's optional arrays (unpaired_off, unpaired_scores; given_cap, or the sweep's minimizer_off,
+        minimizers, regions, explored, read_off, quality) -> (PAIR_MAPQ_RESULT_DT per pair, pair_score per candidate, order per candidate)"""
+        rc, out, pair_score, order = pair_mapq_call(self.lib.vgk_pair_mapq, (self.h,), scheme, cand_off, candidates, counts, **rest)
+        self._check(rc, "vgk_pair_mapq")
+        return out, pair_score, order
+
+    def pair_mapq_limits(self):
+        """-> (candidates of a pair ordered in LDS, lanes per pair, lanes per candidate in the score kernel, 0)"""
+        out = (ctypes.c_uint32 * 4)()
+        self._check(self.lib.vgk_pair_mapq_limits(out), "vgk_pair_mapq_limits")
+        return tuple(int(x) for x in out)
+
+    def pair_mapq_last_ms(self):
+        """device time of the last pair_mapq call in ms: the mates' sweep | the score and pair kernels"""
+        ms = (ctypes.c_double * 2)()
+        self.lib.vgk_pair_mapq_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_pair_mapq_last_ms(self.h, ms), "vgk_pair_mapq_last_ms")
+        return tuple(float(x) for x in ms)
+
+    def pair_mapq_last_launches(self):
+        """pairs of the last pair_mapq call: (in LDS, over the slab, refused by the checks)"""
+        pairs = (ctypes.c_uint64 * 3)()
+        self.lib.vgk_pair_mapq_last_launches.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_pair_mapq_last_launches(self.h, pairs), "vgk_pair_mapq_last_launches")
+        return tuple(int(x) for x in pairs)
+
+    def pair_mapq_last_kernel_launches(self):
+        """kernels the last pair_mapq call launched: (the mates' sweep, the score and pair kernels)"""
+        out = (ctypes.c_uint32 * 2)()
+        self.lib.vgk_pair_mapq_last_kernel_launches.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_pair_mapq_last_kernel_launches(self.h, out), "vgk_pair_mapq_last_kernel_launches")
+        return tuple(int(x) for x in out)
 
     def minimizer_last_ms(self):
         self.lib.vgk_minimizer_last_ms.restype = ctypes.c_double; self.lib.vgk_minimizer_last_ms.argtypes = [ctypes.c_void_p]

@@ -26,6 +26,7 @@
 #include "extension_anchors_device.hpp"
 #include "read_alignments_device.hpp"
 #include "read_mapq_device.hpp"
+#include "pair_mapq_device.hpp"
 
 namespace vgk {
 
@@ -177,6 +178,12 @@ public:
     // order and c[] in LDS, or (p.work) in the slab at p.work_off.  Asynchronous on the main stream.  Optional
     virtual int   run_minimizer_regions(const MqRegionParams& p) { (void)p; return VGK_EUNSUPPORTED; }
     virtual int   run_read_mapq(const MqParams& p) { (void)p; return VGK_EUNSUPPORTED; }
+    // vgk_pair_mapq: the mates' caps alone (mq_cap_one) over the reads p.ids[0 .. p.n), launched as run_read_mapq; every candidate's score
+    // (pair_mapq_device.hpp: pm_candidate_score), a lane per candidate; the pairs p.ids[0 .. p.n) (pm_pair_one), a lane per pair: order and ordered
+    // scores in LDS, or (p.work) in the slab at p.work_off.  Asynchronous on the main stream.  Optional
+    virtual int   run_explored_caps(const MqParams& p) { (void)p; return VGK_EUNSUPPORTED; }
+    virtual int   run_pair_scores(const PmParams& p) { (void)p; return VGK_EUNSUPPORTED; }
+    virtual int   run_pair_mapq(const PmParams& p) { (void)p; return VGK_EUNSUPPORTED; }
     virtual int   run_tail(const TailParams& p, uint32_t threads) = 0;
     virtual int   run_tail_stage(const TStageParams& p, int what) = 0;     // one of the per-item stages of vgk_tail_stage (tail_device.hpp: TS_*)
     virtual int   run_rescue_requests(const RqParams& p, int what) = 0;    // one of the per-pair stages of vgk_rescue_requests (rescue_requests_device.hpp: RQ_*)

@@ -1347,6 +1347,32 @@ __global__ void __launch_bounds__(64) read_mapq_slab_kernel(const MqParams P) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i < P.n) mq_read_one(P, P.ids[i], P.work + P.work_off[i]);
 }
+// ---- a pair's mapping qualities (pair_mapq_device.hpp: pm_candidate_score and pm_pair_one are the rules and the checkers).  The mates' caps: the
+// sweep above without the scores' half (mq_cap_one), cap and verdict per read left in HBM.  Scores: a lane per candidate.  The pairs: a lane per pair;
+// the order and the ordered scores lie in LDS, one slice per lane at an odd stride, for pairs of up to PM_LDS_CANDIDATES candidates; the others come
+// in a launch of their own over slices of a slab.
+__global__ void __launch_bounds__(64) explored_cap_kernel(const MqParams P) {
+    __shared__ uint32_t work[64 * MQ_LDS_STRIDE];
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < P.n) mq_cap_one(P, P.ids[i], work + threadIdx.x * MQ_LDS_STRIDE);
+}
+__global__ void __launch_bounds__(64) explored_cap_slab_kernel(const MqParams P) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < P.n) mq_cap_one(P, P.ids[i], P.work + P.work_off[i]);
+}
+__global__ void __launch_bounds__(256) pair_score_kernel(const PmParams P) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < P.n_candidates) P.pair_score[j] = pm_candidate_score(P, P.cands[j]);
+}
+__global__ void __launch_bounds__(64) pair_mapq_kernel(const PmParams P) {
+    __shared__ uint32_t work[64 * PM_LDS_STRIDE];
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < P.n) pm_pair_one(P, P.ids[i], work + threadIdx.x * PM_LDS_STRIDE);
+}
+__global__ void __launch_bounds__(64) pair_mapq_slab_kernel(const PmParams P) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < P.n) pm_pair_one(P, P.ids[i], P.work + P.work_off[i]);
+}
 __global__ void __launch_bounds__(64) chain_stitch_kernel(const CsParams P, const int what) {
     cs_one(P, what, blockIdx.x * 64 + threadIdx.x);
 }
@@ -2241,6 +2267,26 @@ public:
         if (!p.n) return VGK_OK;
         if (p.work) hipLaunchKernelGGL(read_mapq_slab_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
         else hipLaunchKernelGGL(read_mapq_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_explored_caps(const MqParams& p) override {
+        hipSetDevice(dev);
+        if (!p.n) return VGK_OK;
+        if (p.work) hipLaunchKernelGGL(explored_cap_slab_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
+        else hipLaunchKernelGGL(explored_cap_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_pair_scores(const PmParams& p) override {
+        hipSetDevice(dev);
+        if (!p.n_candidates) return VGK_OK;
+        hipLaunchKernelGGL(pair_score_kernel, dim3((uint32_t)((p.n_candidates + 255) / 256)), dim3(256), 0, stream, p);
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_pair_mapq(const PmParams& p) override {
+        hipSetDevice(dev);
+        if (!p.n) return VGK_OK;
+        if (p.work) hipLaunchKernelGGL(pair_mapq_slab_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
+        else hipLaunchKernelGGL(pair_mapq_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
     int run_minimizer_choose(const MzChooseParams& p, uint32_t blocks) override {

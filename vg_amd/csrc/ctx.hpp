@@ -110,6 +110,10 @@ struct vgk_ctx {
     double read_mapq_ms[2] = {0, 0};   // last vgk_minimizer_regions | vgk_read_mapq
     uint64_t read_mapq_reads[3] = {0, 0, 0};   // reads of the last vgk_read_mapq: swept in LDS | over the slab | refused by the checks
     bool mapq_tables = false;      // phred_to_prob and prob_for_at_least_one are in READMAPQ_TABLES
+    int ensure_mapq_tables();      // ... put there once per context (read_mapq_api.cpp; callers hold `mu`)
+    double pair_mapq_ms[2] = {0, 0};   // last vgk_pair_mapq: the mates' sweep | the score and pair kernels
+    uint32_t pair_mapq_launches[2] = {0, 0};   // kernels the last vgk_pair_mapq launched: the mates' sweep | scores and pairs
+    uint64_t pair_mapq_pairs[3] = {0, 0, 0};   // pairs of the last vgk_pair_mapq: in LDS | over the slab | refused by the checks
     double tail_stage_ms[4] = {0, 0, 0, 0};   // last vgk_tail_stage: tails derived | forest | windows packed | kernels + totals
     double tail_ms = 0;            // device time of the last vgk_tail_forest call
     // the last batch of either call stays resident in the cached device buffers: what a re-run needs to launch it again

@@ -19,6 +19,18 @@ struct Timed { Backend* be; double* ms; Timed(Backend* b, double* m) : be(b), ms
 constexpr uint64_t MQ_MOST = 0xfffffff0ull;
 }  // namespace
 
+// once per context: the shim's own expressions, evaluated here (no pow on the device)
+int vgk_ctx::ensure_mapq_tables() {
+    if (mapq_tables) return VGK_OK;
+    std::vector<double> tab(MQ_PHRED_ENTRIES + MQ_EVENT_ENTRIES);
+    read_mapq_tables(tab.data(), tab.data() + MQ_PHRED_ENTRIES);
+    if (!scratch_dev(READMAPQ_TABLES, tab.data(), sizeof(double) * tab.size())) return VGK_ENOMEM;
+    const int rt = be->sync();                                      // (tab may go)
+    if (rt) return rt;
+    mapq_tables = true;
+    return VGK_OK;
+}
+
 extern "C" {
 
 int vgk_read_mapq_limits(uint32_t out[4]) {
@@ -122,14 +134,8 @@ int vgk_read_mapq(vgk_ctx* ctx, const vgk_read_mapq_scheme* scheme, uint32_t n, 
 
     Backend* be = ctx->be.get();
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (!ctx->mapq_tables) {                                        // once per context: the shim's own expressions, evaluated here (no pow on the device)
-        std::vector<double> tab(MQ_PHRED_ENTRIES + MQ_EVENT_ENTRIES);
-        read_mapq_tables(tab.data(), tab.data() + MQ_PHRED_ENTRIES);
-        if (!ctx->scratch_dev(READMAPQ_TABLES, tab.data(), sizeof(double) * tab.size())) return VGK_ENOMEM;
-        const int rt = be->sync();                                  // (tab may go)
-        if (rt) return rt;
-        ctx->mapq_tables = true;
-    }
+    const int rt = ctx->ensure_mapq_tables();
+    if (rt) return rt;
     MqParams P{};
     P.log_base = scheme->log_base; P.score_scale = scheme->score_scale; P.quality_scale = 10.0 / std::log(10.0);
     P.score_window = scheme->score_window; P.k = scheme->k; P.flags = scheme->flags; P.n_reads = n;

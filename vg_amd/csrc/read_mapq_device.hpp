@@ -15,6 +15,8 @@
 //                   src/mapping_quality_calculator.cpp:26-139), capped by faster_cap over the explored minimizers (src/minimizer_mapper.cpp:2946-3260), the
 //                   escape bonus, round, clamp.  faster_cap's sweep (for_each_agglomeration_interval) keeps a deque of open agglomerations: in the
 //                   explored order — by (agglomeration end, start) — the open set is always a contiguous range, so the deque is a pair of indices.
+//   mq_cap_one      that cap alone, with the sweep's verdict, for the paired rule (pair_mapq_device.hpp), which sums two reads' caps and has no scores
+//                   of a read's own; the quality formula is stated once, as a running sum (mq_sum_*), for both rules.
 //
 // Arithmetic: phred_to_prob and prob_for_at_least_one are tables the HOST makes with the shim's own expressions (read_mapq_tables below) and hands
 // over; no pow is evaluated here.  The OR chain p + q - p q and the column products are not contracted to FMA (MQ_NO_CONTRACT: hipcc contracts by
@@ -63,6 +65,7 @@ struct MqParams {
     const uint32_t* ids; uint32_t n;                             // the reads of a launch
     uint32_t* work; const uint64_t* work_off;                    // the slab of the reads beyond MQ_LDS_EXPLORED, a slice per read of the launch
     vgk_read_mapq_result* out;
+    double* cap_out; int32_t* cap_status;                        // a cap-only launch (mq_cap_one): per read the cap and the sweep's verdict, left in HBM
 };
 
 // ---- agglomerations ---------------------------------------------------------------------------------------------------------------------------------
@@ -103,10 +106,9 @@ VGK_HD bool mq_is_inf(double x) { return x == mq_infinity() || x == -mq_infinity
 
 VGK_HD uint32_t mq_length(const MqParams& P, const vgk_read_minimizer& m) { return (P.flags & VGK_READ_MAPQ_OWN_LENGTH) ? m.reserved : P.k; }
 
-// What must hold before a lane sweeps read r: the verdict is the read's status, and a read that fails is not swept.
-VGK_HD int32_t mq_validate_read(const MqParams& P, uint32_t r) {
-    const bool unmapped = P.unmapped && P.unmapped[r];
-    if (!unmapped && P.score_off[r + 1] == P.score_off[r]) return VGK_EINVAL;                 // (crash_unless(!mappings.empty()))
+// What must hold before a lane sweeps read r: the verdict is the read's status, and a read that fails is not swept.  The sweep's own half (all a
+// cap-only launch checks: pair_mapq_device.hpp), then the read's
+VGK_HD int32_t mq_validate_sweep(const MqParams& P, uint32_t r) {
     if ((P.flags & VGK_READ_MAPQ_NO_EXPLORED_CAP) || !P.qual) return VGK_OK;
     const uint64_t L = P.read_off[r + 1] - P.read_off[r];
     for (uint64_t j = P.min_off[r]; j < P.min_off[r + 1]; ++j) {
@@ -117,6 +119,11 @@ VGK_HD int32_t mq_validate_read(const MqParams& P, uint32_t r) {
     }
     return VGK_OK;
 }
+VGK_HD int32_t mq_validate_read(const MqParams& P, uint32_t r) {
+    const bool unmapped = P.unmapped && P.unmapped[r];
+    if (!unmapped && P.score_off[r + 1] == P.score_off[r]) return VGK_EINVAL;                 // (crash_unless(!mappings.empty()))
+    return mq_validate_sweep(P, r);
+}
 VGK_HD uint32_t mq_count_explored(const MqParams& P, uint32_t r) {
     uint32_t e = 0;
     for (uint64_t j = P.min_off[r]; j < P.min_off[r + 1]; ++j) e += P.explored[j] ? 1u : 0u;
@@ -125,29 +132,41 @@ VGK_HD uint32_t mq_count_explored(const MqParams& P, uint32_t r) {
 
 // MappingQualityCalculator::maximum_mapping_quality_exact over log_base * (scaled score), backwards; first: to_score is the first score's
 VGK_HD double mq_add_log(double x, double y) { return x > y ? x + log1p(exp(y - x)) : y + log1p(exp(x - y)); }
+// The formula as a running sum, for any list handed over from its LAST score to its first (a read's scores here; a pair's ordered scores, its score
+// groups and its mates' unpaired scores in pair_mapq_device.hpp): score = log_base * (the score), m = its multiplicity (1.0: none)
+struct MqSum { double log_sum_exp, to_score, front, front_mult; uint64_t n; };
+VGK_HD MqSum mq_sum_begin() { MqSum s; s.log_sum_exp = mq_lowest(); s.to_score = mq_lowest(); s.front = 0.0; s.front_mult = 1.0; s.n = 0; return s; }
+VGK_HD void mq_sum_add(MqSum& s, double score, double m, bool first) {
+    MQ_NO_CONTRACT
+    s.front = score; s.front_mult = m; ++s.n;                                                 // (the last one handed over is the list's first)
+    if (!first && score >= s.to_score) s.to_score = score;
+    if (m > 1.0) score = score + log(m);
+    s.log_sum_exp = mq_add_log(s.log_sum_exp, score);
+}
+// -> the quality after compute_*_mapping_quality's (int32_t): INT32_MAX when infinite — and for a list without scores
+VGK_HD double mq_sum_quality(const MqSum& s, bool first, double quality_scale) {
+    MQ_NO_CONTRACT
+    double log_sum_exp = s.log_sum_exp, to_score = s.to_score;
+    if (s.n == 1 && !(s.front_mult > 1.0)) log_sum_exp = mq_add_log(log_sum_exp, 0.0);      // the null alignment
+    if (first) to_score = s.front;
+    const double direct = -quality_scale * (0.0 + log1p(-exp((to_score - log_sum_exp) - 0.0)));
+    const double q = mq_is_inf(direct) ? (double)MQ_INT32_MAX : direct;
+    return (double)(int32_t)q;                                                                // compute_*_mapping_quality returns int32_t
+}
 VGK_HD double mq_uncapped(const MqParams& P, uint32_t r) {
     MQ_NO_CONTRACT
     if (P.unmapped && P.unmapped[r]) return 0.0;                                              // not the 50 % the formula would give
     const uint64_t lo = P.score_off[r], n = P.score_off[r + 1] - lo;
     const uint64_t L = P.read_off[r + 1] - P.read_off[r];
     const bool first = (P.flags & VGK_READ_MAPQ_FIRST) != 0;
-    double log_sum_exp = mq_lowest(), to_score = mq_lowest(), front = 0.0;
+    MqSum sum = mq_sum_begin();
     for (uint64_t i = n; i-- > 0;) {
         double scaled = (double)P.scores[lo + i];
         if (P.score_window > 0) scaled = scaled * (double)P.score_window / (double)L;       // (:961-964)
         scaled = scaled * P.score_scale;
-        double score = P.log_base * scaled;
-        if (i == 0) front = score;
-        if (!first && score >= to_score) to_score = score;
-        const double m = P.mult ? P.mult[lo + i] : 1.0;
-        if (m > 1.0) score = score + log(m);
-        log_sum_exp = mq_add_log(log_sum_exp, score);
+        mq_sum_add(sum, P.log_base * scaled, P.mult ? P.mult[lo + i] : 1.0, first);
     }
-    if (n == 1 && !(P.mult && P.mult[lo] > 1.0)) log_sum_exp = mq_add_log(log_sum_exp, 0.0);  // the null alignment
-    if (first) to_score = front;
-    const double direct = -P.quality_scale * (0.0 + log1p(-exp((to_score - log_sum_exp) - 0.0)));
-    const double q = mq_is_inf(direct) ? (double)MQ_INT32_MAX : direct;
-    return (double)(int32_t)q;                                                                // compute_*_mapping_quality returns int32_t
+    return mq_sum_quality(sum, first, P.quality_scale);
 }
 
 // the order word of list entry `idx` (relative to the read's first minimizer)
@@ -248,6 +267,17 @@ VGK_HD void mq_read_one(const MqParams& P, uint32_t r, uint32_t* work) {
         } else { o.uncapped = 0.0; o.explored_cap = 0.0; }
     }
     P.out[r] = o;
+}
+// One read's explored cap alone, as mq_read_one makes it, for a caller that has no scores of the read's own (a pair's mates): P.status holds
+// mq_validate_sweep's verdicts.  A read that is refused or on which the sweep stops: cap 0, its verdict in cap_status
+VGK_HD void mq_cap_one(const MqParams& P, uint32_t r, uint32_t* work) {
+    int32_t status = P.status[r];
+    double cap = 0.0;
+    if (status == VGK_OK) {
+        cap = (P.flags & VGK_READ_MAPQ_NO_EXPLORED_CAP) ? mq_infinity() : mq_explored_cap(P, r, work, &status);
+        if (status != VGK_OK) cap = 0.0;
+    }
+    P.cap_out[r] = cap; P.cap_status[r] = status;
 }
 
 // The tables, made on the host with the expressions of vg_amd/host/mapq_cap.cpp (phred_to_prob, prob_for_at_least_one): phred[256],

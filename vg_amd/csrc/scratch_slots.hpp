@@ -63,6 +63,12 @@ enum Slot : int {
     // bytes and the qualities; the checks' verdicts, the launches' reads, the large reads' slices and their slab; the 24-byte results
     READMAPQ_TABLES, READMAPQ_READ_OFF, READMAPQ_SCORE_OFF, READMAPQ_MIN_OFF, READMAPQ_SCORES, READMAPQ_MULT, READMAPQ_UNMAPPED, READMAPQ_MINS, READMAPQ_REGIONS,
     READMAPQ_EXPLORED, READMAPQ_QUAL, READMAPQ_STATUS, READMAPQ_IDS, READMAPQ_WORK_OFF, READMAPQ_WORK, READMAPQ_OUT,
+    // ---- pair_mapq_api.cpp (nothing stays).  Without given caps the mates' sweep runs over the READMAPQ_* inputs above (the two calls never overlap
+    // under the context lock) and leaves every read's cap and verdict in PAIRMAPQ_CAPS / PAIRMAPQ_CAP_STATUS for the pair kernels; given caps go up
+    // into PAIRMAPQ_CAPS.  The rest: the pairs' offsets, candidates and counts, the mates' unpaired scores, the checks' verdicts, the launches' pairs,
+    // the large pairs' slices and their slab; per candidate its pair score and its place in the order; the 80-byte results
+    PAIRMAPQ_CAND_OFF, PAIRMAPQ_CANDS, PAIRMAPQ_COUNTS, PAIRMAPQ_UNP_OFF, PAIRMAPQ_UNP_SCORES, PAIRMAPQ_CAPS, PAIRMAPQ_CAP_STATUS, PAIRMAPQ_STATUS, PAIRMAPQ_IDS,
+    PAIRMAPQ_WORK_OFF, PAIRMAPQ_WORK, PAIRMAPQ_SCORE, PAIRMAPQ_ORDER, PAIRMAPQ_OUT,
     // ---- gssw_wide_window_api.cpp (nothing stays): the call's problems, reads and verdicts; a sub-batch's windows, per-node temporaries, sizes, their
     // sums, the order's keys; the results and ops packed for the way back.  The arenas the wide kernels read are the WIDE_* buffers (aliases below)
     WIDEWIN_PROBLEMS, WIDEWIN_READS, WIDEWIN_META, WIDEWIN_SUB, WIDEWIN_STORE, WIDEWIN_NODE_FLAGS, WIDEWIN_SLOT_AT, WIDEWIN_PRED_AT, WIDEWIN_WIN_SLOTS,

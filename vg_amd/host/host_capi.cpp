@@ -1410,6 +1410,18 @@ template <class F> void over_reads(uint32_t n, int threads, F one) {
     for (std::thread& t : pool) t.join();
     if (failed) throw std::runtime_error(what);
 }
+// list entries [lo, hi) as faster_cap takes them, and which of them were explored
+void cap_minimizers(uint64_t lo, uint64_t hi, const vgk_read_minimizer* minimizers, const vgk_minimizer_region* regions, const uint8_t* explored, uint32_t k, bool own_length,
+                    std::vector<CapMinimizer>& ms, std::vector<size_t>& ex) {
+    for (uint64_t j = lo; j < hi; ++j) {
+        CapMinimizer m;
+        m.hash = minimizer_hash(minimizers[j].key); m.offset = minimizers[j].offset; m.is_reverse = false;      // (offset is the k-mer's first base always)
+        m.agglomeration_start = regions[j].start; m.agglomeration_length = regions[j].length;
+        m.length = (int32_t)std::min<uint32_t>(own_length ? minimizers[j].reserved : k, 33u);
+        if (explored[j]) ex.push_back(ms.size());
+        ms.push_back(m);
+    }
+}
 }  // namespace
 extern "C" {
 // minimizer_regions for a batch, over vgk_minimizer_regions' arrays plus the reads themselves (the scan looks at every window); rc -1 for a list that
@@ -1438,14 +1450,7 @@ int vgh_read_mapq(const vgk_read_mapq_scheme* scheme, uint32_t n, const uint64_t
             std::vector<double> sc(scores + score_off[r], scores + score_off[r + 1]), mult;
             if (multiplicity) mult.assign(multiplicity + score_off[r], multiplicity + score_off[r + 1]);
             std::vector<CapMinimizer> ms; std::vector<size_t> ex;
-            if (s.use_explored_cap) for (uint64_t j = minimizer_off[r]; j < minimizer_off[r + 1]; ++j) {
-                CapMinimizer m;
-                m.hash = minimizer_hash(minimizers[j].key); m.offset = minimizers[j].offset; m.is_reverse = false;      // (offset is the k-mer's first base always)
-                m.agglomeration_start = regions[j].start; m.agglomeration_length = regions[j].length;
-                m.length = (int32_t)std::min<uint32_t>((scheme->flags & VGK_READ_MAPQ_OWN_LENGTH) ? minimizers[j].reserved : scheme->k, 33u);
-                if (explored[j]) ex.push_back(ms.size());
-                ms.push_back(m);
-            }
+            if (s.use_explored_cap) cap_minimizers(minimizer_off[r], minimizer_off[r + 1], minimizers, regions, explored, scheme->k, (scheme->flags & VGK_READ_MAPQ_OWN_LENGTH) != 0, ms, ex);
             const size_t L = (size_t)(read_off[r + 1] - read_off[r]);
             const ReadMapq q = read_mapq(s, sc, mult, unmapped && unmapped[r], ms, ex, std::string(L, 'N'),
                                          quality ? std::string((const char*)quality + read_off[r], (const char*)quality + read_off[r + 1]) : std::string());
@@ -1474,5 +1479,57 @@ double vgh_read_mapq_direct(const double* scaled_scores, int n, const double* mu
         *sum_others = sum;
     }
     return q;
+}
+}  // extern "C"
+
+// ---- a pair's mapping qualities (pair_mapq.hpp): the checker and CPU baseline of vgk_pair_mapq ---------------------------------------------------------
+#include "pair_mapq.hpp"
+extern "C" {
+// pair_mapq for a batch, over vgk_pair_mapq's arrays and with its outputs; a refused pair: status VGK_EINVAL, the rest of its result 0.  Without given
+// caps the mates' explored caps are read_mapq's (faster_cap over the explored minimizers), a mate on which that stops refusing its pair
+int vgh_pair_mapq(const vgk_pair_mapq_scheme* scheme, uint32_t n, const uint64_t* cand_off, const vgk_pair_candidate* candidates, const vgk_pair_counts* counts,
+                  const uint64_t* unpaired_off, const int32_t* unpaired_scores, const double* given_cap, const uint64_t* minimizer_off, const vgk_read_minimizer* minimizers,
+                  const vgk_minimizer_region* regions, const uint8_t* explored, const uint64_t* read_off, const uint8_t* quality, vgk_pair_mapq_result* out, double* pair_score,
+                  uint32_t* order, int threads) {
+    try {
+        PairMapqScheme s;
+        s.log_base = scheme->log_base; s.fragment_mean = scheme->fragment_mean; s.fragment_sd = scheme->fragment_sd;
+        s.max_multimaps = scheme->max_multimaps; s.max_rescue_attempts = scheme->max_rescue_attempts;
+        const bool capped = !(scheme->flags & VGK_PAIR_MAPQ_NO_EXPLORED_CAP), sweep = capped && !given_cap && quality;
+        ReadMapqScheme cap_scheme;
+        over_reads(n, threads, [&](uint32_t p) {
+            std::vector<PairCandidate> cs;
+            for (uint64_t j = cand_off[p]; j < cand_off[p + 1]; ++j) {
+                const vgk_pair_candidate& c = candidates[j];
+                PairCandidate x;
+                x.score = {{c.score[0], c.score[1]}}; x.fragment_distance = c.distance; x.alignment = {{c.aln[0], c.aln[1]}}; x.better_cluster_count = c.better_cluster_count;
+                x.type = c.type; x.aligned = {{(c.aligned & 1) != 0, (c.aligned & 2) != 0}};
+                cs.push_back(x);
+            }
+            std::array<std::vector<double>, 2> alone; std::array<double, 2> caps; bool mate_stopped = false;
+            for (uint32_t r = 0; r < 2; ++r) {
+                const uint64_t read = 2 * (uint64_t)p + r;
+                if (unpaired_off && unpaired_scores) alone[r].assign(unpaired_scores + unpaired_off[read], unpaired_scores + unpaired_off[read + 1]);
+                caps[r] = capped && given_cap ? given_cap[read] : std::numeric_limits<double>::infinity();
+                if (!sweep) continue;
+                std::vector<CapMinimizer> ms; std::vector<size_t> ex;
+                cap_minimizers(minimizer_off[read], minimizer_off[read + 1], minimizers, regions, explored, scheme->k, false, ms, ex);
+                const size_t L = (size_t)(read_off[read + 1] - read_off[read]);
+                const ReadMapq q = read_mapq(cap_scheme, {}, {}, true, ms, ex, std::string(L, 'N'), std::string((const char*)quality + read_off[read], (const char*)quality + read_off[read + 1]));
+                mate_stopped = mate_stopped || q.stopped;
+                caps[r] = q.explored_cap;
+            }
+            PairMapq q = pair_mapq(s, cs, {{counts[p].unpaired_count[0], counts[p].unpaired_count[1]}}, {{counts[p].rescued_count[0], counts[p].rescued_count[1]}}, alone, caps);
+            for (size_t i = 0; i < cs.size(); ++i) pair_score[cand_off[p] + i] = q.paired_scores[i];
+            if (mate_stopped && !q.stopped) { PairMapq refused; refused.stopped = true; refused.order.resize(cs.size()); for (size_t i = 0; i < cs.size(); ++i) refused.order[i] = i; q = refused; }
+            for (size_t i = 0; i < cs.size(); ++i) order[cand_off[p] + i] = (uint32_t)q.order[i];
+            vgk_pair_mapq_result o;
+            o.mapq[0] = q.mapq[0]; o.mapq[1] = q.mapq[1]; o.status = q.stopped ? VGK_EINVAL : VGK_OK; o.n_chosen = (uint32_t)q.n_chosen; o.uncapped = q.uncapped;
+            o.fragment_cluster_cap = q.fragment_cluster_cap;
+            for (int r = 0; r < 2; ++r) { o.explored_cap[r] = q.explored_cap[r]; o.score_group[r] = q.score_group[r]; o.applied_cap[r] = q.applied_cap[r]; }
+            out[p] = o;
+        });
+        return 0;
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
 }
 }  // extern "C"

@@ -734,8 +734,8 @@ def paired_stage(eng, index, mindex, wl, host_aligner, oriented_len=None, device
     g = wl.graph
     if resident is not None:
         # the product route: the request table from the extension sets on chunked host threads (vg_amd/host/rescue_requests.cpp), no numpy in between
-        return _paired_stage_resident(eng, wl, host_aligner, resident, out, read_score, rescue_stdevs, timing, host_threads, want_ops, t0, t1,
-                                      table_on_device=device if request_table is None else request_table == "device")
+        return dict(_paired_stage_resident(eng, wl, host_aligner, resident, out, read_score, rescue_stdevs, timing, host_threads, want_ops, t0, t1,
+                                           table_on_device=device if request_table is None else request_table == "device"), ext=ext, nodes=nodes)
     full = (res["status"] == 0) & (res["full_length"] != 0)
     a_full, b_full = full[0::2], full[1::2]
     pairs = np.nonzero(a_full != b_full)[0]
@@ -825,7 +825,7 @@ def paired_stage(eng, index, mindex, wl, host_aligner, oriented_len=None, device
     if timing is not None:
         for k, v in (("stage (seeding, extension, tails)", t1 - t0), ("rescue requests (host)", t2 - t1), ("rescue stage (subgraphs, X-drop passes, fix-ups)", t3 - t2)):
             timing[k] = timing.get(k, 0.0) + v
-    return dict(read_score=read_score, rescued=lost, mapped=mapped, requests=req, rescue=outv, pair_score=pair_score, res=res, rescue_ops=ops, rescue_ops_begin=ops_begin,
+    return dict(read_score=read_score, rescued=lost, mapped=mapped, requests=req, rescue=outv, pair_score=pair_score, res=res, ext=ext, nodes=nodes, rescue_ops=ops, rescue_ops_begin=ops_begin,
                 rescue_counts=dict(zip(("first_pass", "scans", "second_pass", "fallbacks", "alg_bytes", "cells"), (int(x) for x in counts)), kernel_ms=float(laps[5])))
 
 
@@ -888,6 +888,61 @@ def _paired_rescue_half(eng, wl, host_aligner, resident, read_score, timing, hos
     return dict(read_score=read_score, rescued=lost_i, mapped=mapped_i, requests=req[:m].copy(), rescue=outv[:m].copy(), pair_score=pair_score, res=res,
                 rescue_ops=ops[:int(written.value)] if want_ops else ops[:0], rescue_ops_begin=ops_begin,
                 rescue_counts=dict(zip(("first_pass", "scans", "second_pass", "fallbacks", "alg_bytes", "cells"), (int(x) for x in counts)), kernel_ms=float(laps[5])))
+
+
+def pair_mapq_inputs(stage, wl):
+    """What vgk_pair_mapq takes of a pair, from paired_stage's answer: ONE candidate per pair — the stage keeps one alignment per mate.  Its scores are the
+    stage's read_score (a rescued mate: the better of the rescued alignment and what the stage had, as the stage's pair_score takes it); its type PAIRED, or
+    RESCUED_FROM_FIRST / _SECOND by the mate rescue started from; a mate is aligned when its score is positive; the fragment distance is the distance between
+    the mates' outer ends in the workload's column coordinates — the same stated stand-in for the absent distance index that the stage uses for rescue —,
+    INT64_MAX where a mate has no position (no extension and no rescued alignment).  -> dict(cand_off, candidates, counts)"""
+    res, ext, nodes = stage["res"], stage["ext"], np.asarray(stage["nodes"])
+    read_score = np.asarray(stage["read_score"], dtype=np.int64); n = len(read_score); n_pairs = n // 2
+    col = np.asarray(wl.graph.col, dtype=np.int64)
+    has = (res["status"] == 0) & (res["n_ext"] > 0)
+    e0 = np.where(has, res["ext_begin"], 0).astype(np.int64)
+    has &= ext["path_len"][e0] > 0
+    first = nodes[np.where(has, ext["path_begin"][e0], 0).astype(np.int64)].astype(np.int64)
+    fwd = (first & 1) == 0
+    outer = np.where(fwd, col[first >> 1] + ext["offset"][e0], col[(first >> 1) + 1] - ext["offset"][e0])      # the fragment's end this mate starts at
+    score = read_score.copy()
+    c = np.zeros(n_pairs, dtype=capi.PAIR_CANDIDATE_DT); counts = np.zeros(n_pairs, dtype=capi.PAIR_COUNTS_DT)
+    lost = np.asarray(stage["rescued"], dtype=np.int64); mapped = np.asarray(stage["mapped"], dtype=np.int64); rescue = np.asarray(stage["rescue"])
+    if len(lost):
+        found = (rescue[:, 1] == 0) & (rescue[:, 4] > 0) & (rescue[:, 0] >= read_score[lost])
+        score[lost] = np.maximum(rescue[:, 0], read_score[lost])
+        # the rescued alignment lies on the forward strand of its subgraph: as the mate's reverse complement (its outer end is the alignment's last column)
+        # when its partner reads forward, else as the mate itself
+        left = col[np.clip(rescue[:, 2], 0, len(col) - 2)] + rescue[:, 3]
+        outer[lost[found]] = np.where(fwd[mapped], left + rescue[:, 5], left)[found]; has[lost[found]] = True
+        c["type"][mapped >> 1] = np.where(mapped & 1, capi.PAIR_RESCUED_FROM_SECOND, capi.PAIR_RESCUED_FROM_FIRST)
+        counts["rescued_count"][mapped >> 1, mapped & 1] = 1
+    c["score"] = score.reshape(-1, 2)
+    both = has[0::2] & has[1::2]
+    c["distance"] = np.where(both, np.abs(outer[1::2] - outer[0::2]), capi.INT64_MAX)
+    c["aligned"] = (score[0::2] > 0) * 1 + (score[1::2] > 0) * 2
+    rescued_unaligned = (c["type"] >= 2) & ((c["aligned"] & np.where(c["type"] == 2, 2, 1)) == 0)
+    c["distance"][rescued_unaligned] = capi.INT64_MAX                                    # (no rescue result: no fragment distance)
+    return dict(cand_off=np.arange(n_pairs + 1, dtype=np.uint64), candidates=c, counts=counts)
+
+
+def pair_mapq(eng, stage, wl, log_base, seeded=None, quality=None, k=29, w=11, max_multimaps=1, max_rescue_attempts=15, flags=0, details=None):
+    """Both mates' mapping qualities for every pair of a paired_stage answer on the device (vgk_pair_mapq, include/vgk_engine.h; pair_mapq_inputs says what
+    the candidates are).  seeded + quality: the seeding's answer for the same reads (seed_long_reads(choice="device"): minimizer_off, minimizers, take) and the
+    reads' Phred bytes laid out as the reads — the mates' explored caps are then swept inside the call, over the agglomerations vgk_minimizer_regions makes
+    (a minimizer is explored when it was taken and has hits, as read_mapq_inputs has it); without them no explored cap.  details: a dict that receives
+    `per_pair` (PAIR_MAPQ_RESULT_DT), `pair_score` and the inputs.  -> int32 [n_pairs, 2]; raveled it is one value per read, as gaf_lines(mapq=...) takes it
+    for one alignment per read"""
+    a = pair_mapq_inputs(stage, wl)
+    if seeded is not None and quality is not None:
+        read_off = np.ascontiguousarray(wl.read_off, dtype=np.uint64); recs = seeded["minimizers"]
+        a.update(minimizer_off=seeded["minimizer_off"], minimizers=recs, regions=eng.minimizer_regions(k, w, read_off, seeded["minimizer_off"], recs),
+                 explored=((np.asarray(seeded["take"]) != 0) & (recs["hits"] > 0)).astype(np.uint8), read_off=read_off, quality=quality)
+    scheme = capi.PairMapqScheme(float(log_base), float(wl.mean), float(wl.sd), int(max_multimaps), int(max_rescue_attempts), int(k), int(flags))
+    per_pair, pair_score, _ = eng.pair_mapq(scheme, **a)
+    if details is not None:
+        details.update(a, per_pair=per_pair, pair_score=pair_score, scheme=scheme)
+    return per_pair["mapq"].copy()
 
 
 class HostAlignerHandle:

@@ -1563,3 +1563,147 @@ class ReadMapqWorkload:
         a["read_off"], a["quality"] = pick(self.read_off, a["quality"])
         a["unmapped"] = self.unmapped[reads]
         return a
+
+
+# ---- a pair's mapping qualities (vgk_pair_mapq, include/vgk_engine.h) -----------------------------------------------------------------------------
+class PairMapqWorkload:
+    """Pairs with their candidate pairings, counts, unpaired scores and explored caps for vgk_pair_mapq (include/vgk_engine.h).  A pair's mates are reads of
+    a ReadMapqWorkload (its lists, agglomerations, explored bytes and qualities, the reads its sweep stops on and the ones at the LDS limit of that sweep
+    included), dealt round and round; the candidates come from a seeded generator that plants what the rule must reach: 0 .. 8 candidates, counts at the
+    LDS limit, one below, one above and a few of several hundred; equal pair scores (also across the max_multimaps cut); a likelihood that drops the sum
+    below the worse mate's score; a distance at the mean; unreachable mates; winners of all four types; pairs of rescued candidates only (multiplicities) and
+    mixed ones; a rescued candidate with an unaligned mate as winner and as loser; a first score of 0; every better_cluster_count of interest; and the
+    pairs that are refused (refusals: pair -> why).  Score gaps are small (the quality is finite) or large (it is infinite): none lies where the sum of
+    exp(other - best) is about 1e-14, the edge of the infinite case, which two correct libraries may see from different sides.
+    `variants` are the schemes the corpus is run under; arrays(variant) gives a call's arguments."""
+
+    KINDS = ("paired", "mixed", "rescued", "unpaired", "rescued+unpaired")
+
+    def __init__(self, n_pairs=20000, seed=0, log_base=1.3862943611198906, lds_limit=64, mean=400.0, sd=40.0, max_rescue_attempts=15, base=None):
+        rng = np.random.default_rng(seed)
+        self.n = n = int(n_pairs); self.log_base = float(log_base); self.mean = float(mean); self.sd = float(sd); self.max_rescue_attempts = int(max_rescue_attempts)
+        self.base = base if base is not None else ReadMapqWorkload(n_short=1500, n_long=4, seed=seed + 1, log_base=log_base)
+        self.k = self.base.k
+        limit = int(lds_limit)
+        planted_counts = list(range(9)) + [limit - 1, limit, limit + 1, 300, 450, 600]
+        bad = ["type above 3", "no rescue attempts", "unaligned rescued mate with a distance"]
+        flavours = ["equal", "zero", "far", "at mean", "unreachable", "unaligned rescued winner", "unaligned rescued loser", "low single"]
+        cands, counts, alone, alone_off, cand_off = [], np.zeros(n, dtype=capi.PAIR_COUNTS_DT), [], [0], [0]
+        self.kind, self.flavour, self.refusals, self.special = [], [], {}, {}
+        for p in range(n):
+            kind = self.KINDS[p % 5] if p < 200 else self.KINDS[int(rng.choice(5, p=[0.45, 0.15, 0.2, 0.1, 0.1]))]
+            C = planted_counts[p] if p < len(planted_counts) else int(rng.choice([1, 2, 3, 4, 5, 6, 7, 8, 12], p=[0.2, 0.2, 0.15, 0.12, 0.1, 0.08, 0.06, 0.05, 0.04]))
+            flavour = flavours[(p // 5) % len(flavours)] if 20 <= p < 180 else ("" if rng.random() < 0.8 else flavours[int(rng.integers(len(flavours)))])
+            if p < len(planted_counts):
+                flavour = ""; self.special["%d candidates" % C] = p
+            if 180 <= p < 180 + 3 * len(bad):
+                flavour = bad[(p - 180) % len(bad)]; kind = "rescued" if p % 2 else "mixed"; C = max(C, 2)
+                self.refusals[p] = flavour
+            if flavour in ("unaligned rescued winner", "unaligned rescued loser"):
+                kind = "rescued" if flavour.endswith("winner") else "mixed"; C = max(C, 2)
+            if flavour == "low single":
+                C = 1
+            if flavour in ("equal", "zero", "far", "at mean", "unreachable"):
+                C = max(C, 1 if flavour != "equal" else 2 + (p % 5))
+            self.kind.append(kind); self.flavour.append(flavour)
+            c = np.zeros(C, dtype=capi.PAIR_CANDIDATE_DT)
+            top = rng.integers(60, 151, 2)
+            c["score"] = top[None, :] - rng.integers(0, 7, (C, 2))
+            c["distance"] = np.rint(mean + sd * rng.normal(0, 1, C)).astype(np.int64)
+            odd = rng.random(C)
+            c["distance"][odd < 0.06] = int(mean + 40 * sd); c["distance"][(odd >= 0.06) & (odd < 0.12)] = capi.INT64_MAX; c["distance"][(odd >= 0.12) & (odd < 0.16)] = int(mean)
+            c["aln"] = rng.integers(0, 3, (C, 2))
+            c["better_cluster_count"] = rng.choice([0, 1, 2, 3, 7, 1000], C)
+            if C:
+                c["better_cluster_count"][:] = np.where(rng.random(C) < 0.5, c["better_cluster_count"], c["better_cluster_count"][0])
+            c["aligned"] = np.where(rng.random(C) < 0.03, rng.integers(0, 3, C), 3)
+            t = {"paired": [0], "mixed": [0, 2, 3], "rescued": [2, 3], "unpaired": [1], "rescued+unpaired": [1, 2, 3]}[kind]
+            c["type"] = rng.choice(t, C)
+            if kind == "mixed" and C:
+                c["type"][int(rng.integers(C))] = 0
+            if flavour == "equal":
+                c[:] = c[0]
+                if C > 2 and p % 2:
+                    c["aln"] = rng.integers(0, 2, (C, 2))
+            elif flavour == "zero":
+                c["score"] = 0; c["distance"] = int(mean)
+            elif flavour == "far":
+                c["distance"] = int(mean + 40 * sd)
+            elif flavour == "at mean":
+                c["distance"] = int(mean)
+            elif flavour == "unreachable":
+                c["distance"] = capi.INT64_MAX
+            elif flavour == "low single":
+                c["score"] = rng.integers(2, 8, (1, 2)); c["distance"] = int(mean); c["aligned"] = 3
+            rescued = (c["type"] == 2) | (c["type"] == 3)
+            lost = np.where(c["type"] == 2, 2, 1).astype(np.uint8)              # the rescued mate's bit
+            unaligned = rescued & (rng.random(C) < 0.08)
+            if flavour == "unaligned rescued winner":
+                unaligned = rescued
+            if flavour == "unaligned rescued loser":
+                j = int(rng.integers(1, C)); c["type"][j] = 2 + (p % 2); c["type"][0] = 0; unaligned = np.zeros(C, dtype=bool); unaligned[j] = True
+                lost = np.where(c["type"] == 2, 2, 1).astype(np.uint8)
+            c["aligned"] = np.where(rescued | unaligned, np.where(unaligned, 3 & ~lost, 3), c["aligned"])
+            c["distance"][unaligned] = capi.INT64_MAX
+            counts["unpaired_count"][p] = np.where(rng.random(2) < 0.3, 0, rng.integers(1, 41, 2)); counts["rescued_count"][p] = rng.integers(1, 21, 2)
+            if flavour == "type above 3":
+                c["type"][C - 1] = 4 + (p % 3)
+            elif flavour == "no rescue attempts":
+                c["type"][0] = 2; c["aligned"][0] = 3; c["distance"][0] = int(mean); counts["rescued_count"][p][0] = 0
+            elif flavour == "unaligned rescued mate with a distance":
+                c["type"][0] = 3; c["aligned"][0] = 2; c["distance"][0] = int(mean) + 7
+            cands.append(c); cand_off.append(cand_off[-1] + C)
+            for r in range(2):
+                m = int(rng.choice([0, 1, 1, 2, 3, 4]))
+                s = [] if not m else ([int(rng.integers(2, 8))] if m == 1 and rng.random() < 0.3 else [int(top[r])] + [int(top[r] - x) for x in rng.integers(0, 10, m - 1)])
+                alone += s; alone_off.append(alone_off[-1] + len(s))
+        self.cand_off = np.array(cand_off, dtype=np.uint64); self.candidates = np.concatenate(cands); self.counts = counts
+        self.unpaired_off = np.array(alone_off, dtype=np.uint64); self.unpaired_scores = np.array(alone, dtype=np.int32)
+        caps = rng.uniform(0.0, 70.0, 2 * n); odd = rng.random(2 * n)
+        caps[odd < 0.05] = -0.0; caps[(odd >= 0.05) & (odd < 0.08)] = np.inf
+        self.given_cap = caps
+        # the mates: the base workload's reads round and round (its length is odd: a pair's two reads change from round to round)
+        self.read_of = (np.arange(2 * n, dtype=np.int64) + 7) % self.base.n
+        self.mates = self.base.arrays({}, self.read_of)
+        sweep_stops = [r for r, what in self.base.stop_kinds.items() if what in ("impossible to disrupt", "region behind the read")]
+        self.mate_stops = {int(p): "a mate the sweep stops on" for p in np.nonzero(np.isin(self.read_of, sweep_stops))[0] // 2}
+        self.variants = [dict(name="given caps, one mapping", caps="given", max_multimaps=1), dict(name="given caps, four mappings", caps="given", max_multimaps=4),
+                         dict(name="caps in the call", caps="computed", max_multimaps=4), dict(name="caps in the call, no qualities", caps="computed", quality=False, max_multimaps=1),
+                         dict(name="no explored cap", caps="given", flags=capi.PAIR_MAPQ_NO_EXPLORED_CAP, max_multimaps=4)]
+
+    def stops(self, variant):
+        """the pairs that must answer VGK_EINVAL under `variant`: pair -> why"""
+        out = dict(self.refusals)
+        if variant.get("caps") == "computed" and variant.get("quality", True) and not int(variant.get("flags", 0)) & capi.PAIR_MAPQ_NO_EXPLORED_CAP:
+            out.update({p: why for p, why in self.mate_stops.items() if p not in out})
+        return out
+
+    def scheme(self, variant):
+        return capi.PairMapqScheme(self.log_base, self.mean, self.sd, int(variant.get("max_multimaps", 1)), self.max_rescue_attempts, self.k, int(variant.get("flags", 0)))
+
+    def arrays(self, variant, pairs=None):
+        """the arguments of capi.pair_mapq_call behind `scheme`, for all pairs or the pairs `pairs`"""
+        given = variant.get("caps", "given") == "given"
+        m = self.mates
+        a = dict(cand_off=self.cand_off, candidates=self.candidates, counts=self.counts, unpaired_off=self.unpaired_off, unpaired_scores=self.unpaired_scores,
+                 given_cap=self.given_cap if given else None)
+        if not given:
+            a.update(minimizer_off=m["minimizer_off"], minimizers=m["minimizers"], regions=m["regions"], explored=m["explored"], read_off=m["read_off"],
+                     quality=m["quality"] if variant.get("quality", True) else None)
+        if pairs is None:
+            return a
+        pairs = np.asarray(pairs, dtype=np.int64); reads = np.stack([2 * pairs, 2 * pairs + 1], axis=1).ravel()
+
+        def pick(off, which, *arrs):
+            off = off.astype(np.int64); size = off[which + 1] - off[which]
+            idx = np.repeat(off[which], size) + (np.arange(int(size.sum())) - np.repeat(np.cumsum(size) - size, size))
+            return (np.concatenate([[0], np.cumsum(size)]).astype(np.uint64),) + tuple(None if x is None else x[idx] for x in arrs)
+        a["cand_off"], a["candidates"] = pick(self.cand_off, pairs, self.candidates)
+        a["counts"] = self.counts[pairs]
+        a["unpaired_off"], a["unpaired_scores"] = pick(self.unpaired_off, reads, self.unpaired_scores)
+        if given:
+            a["given_cap"] = self.given_cap[reads]
+        else:
+            a["minimizer_off"], a["minimizers"], a["regions"], a["explored"] = pick(m["minimizer_off"], reads, m["minimizers"], m["regions"], m["explored"])
+            a["read_off"], a["quality"] = pick(m["read_off"], reads, a["quality"])
+        return a
