@@ -122,7 +122,8 @@ tests/emu/pair_mapq_san: tests/emu/pair_mapq_driver.cpp $(LIB_HDRS)
 # gapless_device.hpp and its per-thread slabs on the limits the edge corpus of tests/test_gapless_definition.py sits on
 gapless_san: tests/emu/gapless_san
 SAN_FLAGS := -O1 -g -std=c++17 -Iinclude -Wall -DVGK_PK_CHECK -fsanitize=address,undefined -fno-sanitize-recover=undefined
-SAN_OBJS := $(patsubst vg_amd/csrc/%.cpp,tests/emu/san_obj/%.o,$(wildcard vg_amd/csrc/*.cpp)) tests/emu/san_obj/backend_emu.o tests/emu/san_obj/gapless_san_main.o
+SAN_ENGINE_OBJS := $(patsubst vg_amd/csrc/%.cpp,tests/emu/san_obj/%.o,$(wildcard vg_amd/csrc/*.cpp)) tests/emu/san_obj/backend_emu.o
+SAN_OBJS := $(SAN_ENGINE_OBJS) tests/emu/san_obj/gapless_san_main.o
 tests/emu/san_obj/%.o: vg_amd/csrc/%.cpp $(LIB_HDRS)
 	@mkdir -p tests/emu/san_obj
 	$(CXX) $(SAN_FLAGS) -c $< -o $@
@@ -132,3 +133,11 @@ tests/emu/san_obj/%.o: tests/emu/%.cpp $(LIB_HDRS)
 tests/emu/gapless_san: $(SAN_OBJS)
 	$(CXX) -fsanitize=address,undefined -o $@ $(SAN_OBJS) -lpthread
 .PHONY: gapless_san
+
+# test-only: vgk_haplo_create + vgk_chain_stitch on the emulated backend as a program of its own under the host sanitizers (the same sanitized
+# engine objects, its own main) — the lane code of chain_device.hpp on the calls of tests/test_chain_stitch_definition.py
+chainstitch_san: tests/emu/chain_stitch_san
+CHAINSTITCH_SAN_OBJS := $(SAN_ENGINE_OBJS) tests/emu/san_obj/chain_stitch_san_main.o
+tests/emu/chain_stitch_san: $(CHAINSTITCH_SAN_OBJS)
+	$(CXX) -fsanitize=address,undefined -o $@ $(CHAINSTITCH_SAN_OBJS) -lpthread
+.PHONY: chainstitch_san

@@ -48,9 +48,11 @@ int vgk_chain_stitch(vgk_ctx* ctx, const vgk_haplo* index, const vgk_chain_piece
     auto al = [](uint64_t b) { return (b + 15) & ~15ull; };
     const uint64_t b_off = al(sizeof(uint64_t) * (uint64_t)R), b_pc = al(sizeof(vgk_chain_piece) * n_pieces), b_nd = al(sizeof(uint32_t) * n_nodes),
                    b_mp = al(sizeof(vgk_chain_mapping) * n_mappings), b_ed = al(sizeof(uint32_t) * n_edits);
-    const uint64_t up_bytes = b_off + b_pc + b_nd + b_mp + b_ed + 16;
+    const uint64_t b_in = b_off + b_pc + b_nd + b_mp + b_ed + 16;                     // (behind the inputs: the two 64-bit bound totals, uploaded as zeros)
+    const uint64_t up_bytes = b_in + 16;
     char* up = H.up.get(be, up_bytes);
     if (!up) return VGK_ENOMEM;
+    std::memset(up + b_in, 0, 16);
     std::memcpy(up, piece_off, sizeof(uint64_t) * (size_t)R);
     if (n_pieces) std::memcpy(up + b_off, pieces, sizeof(vgk_chain_piece) * n_pieces);
     if (n_nodes) std::memcpy(up + b_off + b_pc, nodes, sizeof(uint32_t) * n_nodes);
@@ -67,19 +69,20 @@ int vgk_chain_stitch(vgk_ctx* ctx, const vgk_haplo* index, const vgk_chain_piece
     P.mappings = (const vgk_chain_mapping*)(d_up + b_off + b_pc + b_nd); P.edits = (const uint32_t*)(d_up + b_off + b_pc + b_nd + b_mp);
     P.bound = d_tab; P.slot = d_tab + 2 * (size_t)R; P.count = d_tab + 4 * (size_t)R; P.out_slot = d_tab + 6 * (size_t)R;
     P.res = d_res; P.out_res = d_res + n_reads;
+    P.bound_total = (unsigned long long*)(d_up + b_in);
     // 1. bounds per read (entry n_reads of either half: 0), their prefix sums, the totals
     if ((rc = be->run_chain_stitch(P, CS_BOUND))) return rc;
     if ((rc = be->scan_u32(P.bound, d_tab + 2 * (size_t)R, R))) return rc;
     if ((rc = be->scan_u32(P.bound + R, d_tab + 3 * (size_t)R, R))) return rc;
     uint32_t* tails = H.tails.get(be, 8);
     if (!tails) return VGK_ENOMEM;
-    if ((rc = be->download(&tails[0], d_tab + 2 * (size_t)R + n_reads, sizeof(uint32_t)))) return rc;      // (the scans' last entries: all mappings | all edit runs at most)
-    if ((rc = be->download(&tails[1], d_tab + 3 * (size_t)R + n_reads, sizeof(uint32_t)))) return rc;
-    // (a 32-bit prefix sum that wrapped: the sum of per-read bounds each < 2^32 — caught by comparing with what the inputs can make at most)
-    const uint64_t most_m = n_mappings + (uint64_t)n_nodes + n_pieces + (links ? ctx->wfa_out.path_cap + ctx->wfa_out.n : 0);
-    const uint64_t most_e = n_edits + (uint64_t)n_nodes + n_pieces + (links ? ctx->wfa_out.path_cap + ctx->wfa_out.edit_cap : 0);
-    if (most_m > 0xfffffff0ull || most_e > 0xfffffff0ull) return VGK_ETOOBIG;
-    const uint64_t work_m = tails[0], work_e = tails[1];
+    if ((rc = be->download(&tails[4], P.bound_total, 2 * sizeof(uint64_t)))) return rc;      // (all mappings | all edit runs at most, summed in 64 bits by CS_BOUND itself)
+    uint64_t work_m, work_e;
+    std::memcpy(&work_m, &tails[4], sizeof work_m); std::memcpy(&work_e, &tails[6], sizeof work_e);
+    // The prefix sums above are 32-bit: they are what they seem only when the totals fit.  The totals are sums of per-read bounds (each saturated
+    // at 0xffffffff, so that one saturated read alone is past the limit) made from ranges inside the caller's arrays — pieces may name the same
+    // stretch of `nodes` any number of times, so the arrays' sizes say nothing about them.  Nothing is allocated from a total that does not fit.
+    if (work_m > 0xfffffff0ull || work_e > 0xfffffff0ull) return VGK_ETOOBIG;
     P.work_m = (vgk_chain_mapping*)ctx->ensure_scratch(CHAIN_WORK_M, sizeof(vgk_chain_mapping) * (work_m + 1));
     P.work_e = (uint32_t*)ctx->ensure_scratch(CHAIN_WORK_E, sizeof(uint32_t) * (work_e + 1));
     if (!P.work_m || !P.work_e) return VGK_ENOMEM;

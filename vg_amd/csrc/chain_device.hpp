@@ -26,6 +26,7 @@ struct CsParams {
     // what the last vgk_wfa_extend call left in HBM (results in problem order; paths and edit runs in completion order)
     const vgk_wfa_result* link_res; const uint32_t* link_paths; const uint32_t* link_edits; uint32_t n_links; uint64_t link_path_cap, link_edit_cap;
     uint32_t* bound;                                            // [2 (n_reads + 1)] CS_BOUND: mappings | edit runs per read at most (entry n_reads of either half = 0)
+    unsigned long long* bound_total;                            // [2] CS_BOUND: the sums of either half in 64 bits (zero before the stage): what the 32-bit prefix sums cannot tell when they wrap
     const uint32_t* slot;                                       // [2 (n_reads + 1)] their exclusive prefix sums, half by half
     vgk_chain_mapping* work_m; uint32_t* work_e;                // the stretches
     vgk_chain_result* res;                                      // [n_reads] CS_STITCH: status, sizes; mapping_begin / edit_begin inside the work arrays
@@ -46,27 +47,51 @@ VGK_HD bool cs_link_ok(const CsParams& P, const vgk_chain_piece& pc) {
 
 // ---- CS_BOUND --------------------------------------------------------------------------------------------------------------------------
 // A WFAAlignment of p nodes and e runs makes at most max(p, 1) mappings and e + p edits (a run is cut at most once per node boundary);
-// a stated Path makes what it holds.  Nothing in simplify makes more of either.
+// a stated Path makes what it holds.  Nothing in simplify makes more of either.  What CS_STITCH refuses — a range past its array, a node beyond
+// the index, an unknown kind: the same tests as in cs_stitch_one — ends the read there, so neither it nor anything behind it counts: a bound
+// is always made of ranges that lie inside the caller's arrays.  Either bound saturates at 0xffffffff; the sums over all reads are kept in
+// 64 bits beside the per-read values, so that the host sees a total the 32-bit prefix sums would wrap on.
+// (On the device the 64 lanes of a wavefront add their values up across the lanes and lane 0 adds the sum to the total: one atomic per wavefront
+// and total instead of one per lane on one address.  Every lane of the launch comes here for that, the ones behind the last read with nothing.)
+#if defined(__HIP_DEVICE_COMPILE__)
+VGK_HD void cs_add64_wave(unsigned long long* p, unsigned long long v) {
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(p, v);
+}
+#else
+VGK_HD void cs_add64_wave(unsigned long long* p, unsigned long long v) { *p += v; }
+#endif
 VGK_HD void cs_bound_one(const CsParams& P, uint32_t r) {
     uint64_t m = 0, e = 0;
     if (r < P.n_reads) {
+        // (no early way out of either loop: a lane's time here is its chain of dependent loads, and a load that waits for the test of the one before it
+        // cannot be in flight beside it — leaving at the first refusal cost 0.11 ms on a 4 000-read call.  `live` ends the counting instead; every
+        // load stays behind its own range test.)
+        bool live = true;
         for (uint64_t k = P.piece_off[r]; k < P.piece_off[r + 1]; ++k) {
             const vgk_chain_piece pc = P.pieces[k];
+            uint64_t pm = 0, pe = 0; bool ok = false;
             if (pc.kind == (uint32_t)VGK_PIECE_LINK) {
-                if (!cs_link_ok(P, pc)) continue;
-                const vgk_wfa_result& w = P.link_res[pc.link];
-                m += w.path_len ? w.path_len : 1u; e += (uint64_t)w.n_edits + w.path_len;
+                ok = cs_link_ok(P, pc);
+                if (ok) { const vgk_wfa_result& w = P.link_res[pc.link]; pm = w.path_len ? w.path_len : 1u; pe = (uint64_t)w.n_edits + w.path_len; }
             } else if (pc.kind == (uint32_t)VGK_PIECE_ALIGNMENT) {
-                m += pc.path_len ? pc.path_len : 1u; e += (uint64_t)pc.n_edits + pc.path_len;
+                ok = (uint64_t)pc.path_begin + pc.path_len <= P.n_nodes && (uint64_t)pc.edit_begin + pc.n_edits <= P.n_edits;
+                if (ok) { pm = pc.path_len ? pc.path_len : 1u; pe = (uint64_t)pc.n_edits + pc.path_len; }
             } else if (pc.kind == (uint32_t)VGK_PIECE_PATH) {
-                if ((uint64_t)pc.path_begin + pc.path_len > P.n_mappings) continue;
-                m += pc.path_len;
-                for (uint32_t q = 0; q < pc.path_len; ++q) e += P.mappings[pc.path_begin + q].n_edits;
+                ok = (uint64_t)pc.path_begin + pc.path_len <= P.n_mappings;
+                if (ok) for (uint32_t q = 0; q < pc.path_len; ++q) {               // the mappings in front of the first refused one count: CS_STITCH writes them
+                    const vgk_chain_mapping g = P.mappings[pc.path_begin + q];
+                    ok = ok && (uint64_t)g.edit_begin + g.n_edits <= P.n_edits && (g.node == VGK_WFA_NO_NODE || g.node < P.index.n_oriented);
+                    pm += ok ? 1u : 0u; pe += ok ? g.n_edits : 0u;
+                }
             }
+            if (live) { m += pm; e += pe; }
+            live = live && ok;
         }
     }
-    P.bound[r] = m < 0xffffffffull ? (uint32_t)m : 0xffffffffu;
-    P.bound[(size_t)P.n_reads + 1 + r] = e < 0xffffffffull ? (uint32_t)e : 0xffffffffu;
+    const uint32_t bm = m < 0xffffffffull ? (uint32_t)m : 0xffffffffu, be = e < 0xffffffffull ? (uint32_t)e : 0xffffffffu;
+    if (r <= P.n_reads) { P.bound[r] = bm; P.bound[(size_t)P.n_reads + 1 + r] = be; }
+    cs_add64_wave(P.bound_total, bm); cs_add64_wave(P.bound_total + 1, be);
 }
 
 // ---- CS_STITCH -------------------------------------------------------------------------------------------------------------------------
@@ -286,7 +311,7 @@ VGK_HD void cs_gather_one(const CsParams& P, uint32_t r, uint32_t lane, uint32_t
 
 // what one lane does in stage `what`: item r of n_reads + 1 (the bounds' and sizes' last entries are 0: the prefix sums' totals land there)
 VGK_HD void cs_one(const CsParams& P, int what, uint32_t r) {
-    if (what == CS_BOUND) { if (r <= P.n_reads) cs_bound_one(P, r); }
+    if (what == CS_BOUND) cs_bound_one(P, r);
     else if (what == CS_STITCH) { if (r < P.n_reads) cs_stitch_one(P, r); else if (r == P.n_reads) { P.count[r] = 0; P.count[(size_t)P.n_reads + 1 + r] = 0; } }
 }
 
