@@ -141,3 +141,10 @@ CHAINSTITCH_SAN_OBJS := $(SAN_ENGINE_OBJS) tests/emu/san_obj/chain_stitch_san_ma
 tests/emu/chain_stitch_san: $(CHAINSTITCH_SAN_OBJS)
 	$(CXX) -fsanitize=address,undefined -o $@ $(CHAINSTITCH_SAN_OBJS) -lpthread
 .PHONY: chainstitch_san
+
+# test-only: the launch plans of launch_split.hpp (which item in which launch, which slice of the slab) against a brute force, as a program of its
+# own under the host sanitizers — the header alone, no engine object
+launch_split_san: tests/emu/launch_split_san
+tests/emu/launch_split_san: tests/emu/launch_split_san_main.cpp vg_amd/csrc/launch_split.hpp include/vgk.h
+	$(CXX) $(SAN_FLAGS) -Ivg_amd/csrc -o $@ $<
+.PHONY: launch_split_san

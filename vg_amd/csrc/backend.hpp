@@ -162,6 +162,9 @@ public:
     virtual int   run_minimizer(const MinimizerParams& p) = 0;            // minimizer_device.hpp: one lane per read, pass p.pass
     virtual int   run_minimizer_list(const MzListParams& p) = 0;           // mz_list_one for reads [0, n] (pass p.pass), asynchronous on the main stream
     virtual int   run_minimizer_seeds_of(const MzSeedsOfParams& p) = 0;    // mz_seeds_of_one for minimizers [0, n]
+    // The seven families below launch in pairs (launch_split.hpp makes the plan, ctx.hpp's launch_split() the calls): p.ids[0 .. p.n) are the items of ONE
+    // launch, which the caller took from the plan's ids — the LDS items with p.slab / p.work null, then the large ones with the slab attached; p.work_off[j]
+    // is the slice of p.ids[j], the j-th item of that launch.  The caller sends no empty launch; a backend answers VGK_OK to one all the same.
     // find_seeds' whole choice for the reads p.ids[0 .. p.n) (mz_choose_one's rule), `blocks` workgroups: in LDS, or (p.slab) over the slab.  Optional
     virtual int   run_minimizer_choose(const MzChooseParams& p, uint32_t blocks) { (void)p; (void)blocks; return VGK_EUNSUPPORTED; }
     // one stage of vgk_chain_items (chain_items_device.hpp: CI_RUN_*), asynchronous on the main stream: a lane per candidate (legality, scatter), or

@@ -2201,6 +2201,12 @@ public:
         hipLaunchKernelGGL(minimizer_seeds_of_kernel, dim3((p.n + 256) / 256), dim3(256), 0, stream, p);
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
+    // one launch of a launch_split.hpp pair, wavefronts of 64 lanes: the kernel whose working set lies in LDS (lds_bytes of it dynamic), or its slab twin
+    template <class P> int launch_lds_or_slab(void (*lds_kernel)(const P), void (*slab_kernel)(const P), bool slab, uint32_t grid, uint32_t lds_bytes, const P& p) {
+        if (slab) hipLaunchKernelGGL(slab_kernel, dim3(grid), dim3(64), 0, stream, p);
+        else hipLaunchKernelGGL(lds_kernel, dim3(grid), dim3(64), lds_bytes, stream, p);
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
     int run_chain_items(const CiParams& p, int what, uint32_t blocks) override {
         hipSetDevice(dev);
         if (what == CI_RUN_LEGAL || what == CI_RUN_SCATTER) {
@@ -2211,13 +2217,9 @@ public:
         } else {
             if (!blocks) return VGK_OK;
             if (!p.slab && (p.lds_np > CI_LDS_MAX || (p.lds_np & (p.lds_np - 1u)))) return VGK_EINVAL;
-            if (what == CI_RUN_DP) {
-                if (p.slab) hipLaunchKernelGGL(chain_items_dp_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
-                else hipLaunchKernelGGL(chain_items_dp_kernel, dim3(blocks), dim3(64), ci_dp_lds_bytes(p.lds_np), stream, p);
-            } else if (what == CI_RUN_TRACE) {
-                if (p.slab) hipLaunchKernelGGL(chain_items_trace_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
-                else hipLaunchKernelGGL(chain_items_trace_kernel, dim3(blocks), dim3(64), ci_trace_lds_bytes(p.lds_np), stream, p);
-            } else return VGK_EINVAL;
+            if (what == CI_RUN_DP) return launch_lds_or_slab(chain_items_dp_kernel, chain_items_dp_slab_kernel, p.slab, blocks, ci_dp_lds_bytes(p.lds_np), p);
+            if (what == CI_RUN_TRACE) return launch_lds_or_slab(chain_items_trace_kernel, chain_items_trace_slab_kernel, p.slab, blocks, ci_trace_lds_bytes(p.lds_np), p);
+            return VGK_EINVAL;
         }
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
@@ -2233,13 +2235,8 @@ public:
             if (!blocks) return VGK_OK;
             if (!p.slab && (p.lds_np > std::max(EA_LDS_SEEDS, EA_LDS_EXT) || (p.lds_np & (p.lds_np - 1u)))) return VGK_EINVAL;
             const uint32_t lds = (uint32_t)ea_work_bytes(p.lds_np, EA_LDS_SEEDS);
-            if (what == EA_RUN_SORT) {
-                if (p.slab) hipLaunchKernelGGL(extension_anchors_sort_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
-                else hipLaunchKernelGGL(extension_anchors_sort_kernel, dim3(blocks), dim3(64), lds, stream, p);
-            } else {
-                if (p.slab) hipLaunchKernelGGL(extension_anchors_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
-                else hipLaunchKernelGGL(extension_anchors_kernel, dim3(blocks), dim3(64), lds, stream, p);
-            }
+            if (what == EA_RUN_SORT) return launch_lds_or_slab(extension_anchors_sort_kernel, extension_anchors_sort_slab_kernel, p.slab, blocks, lds, p);
+            return launch_lds_or_slab(extension_anchors_kernel, extension_anchors_slab_kernel, p.slab, blocks, lds, p);
         } else return VGK_EINVAL;
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
@@ -2247,8 +2244,7 @@ public:
         hipSetDevice(dev);
         if (what == RA_RUN_SELECT) {
             if (!p.n) return VGK_OK;
-            if (p.work && p.ids) hipLaunchKernelGGL(read_alignments_select_slab_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
-            else hipLaunchKernelGGL(read_alignments_select_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
+            return launch_lds_or_slab(read_alignments_select_kernel, read_alignments_select_slab_kernel, p.work && p.ids, (p.n + 63) / 64, 0, p);
         } else if (what == RA_RUN_COUNT || what == RA_RUN_EMIT || what == RA_RUN_TAILS) {
             const uint32_t items = what == RA_RUN_TAILS ? p.n_tails : p.n_reads;
             if (!items) return VGK_OK;
@@ -2265,16 +2261,12 @@ public:
     int run_read_mapq(const MqParams& p) override {
         hipSetDevice(dev);
         if (!p.n) return VGK_OK;
-        if (p.work) hipLaunchKernelGGL(read_mapq_slab_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
-        else hipLaunchKernelGGL(read_mapq_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+        return launch_lds_or_slab(read_mapq_kernel, read_mapq_slab_kernel, p.work, (p.n + 63) / 64, 0, p);
     }
     int run_explored_caps(const MqParams& p) override {
         hipSetDevice(dev);
         if (!p.n) return VGK_OK;
-        if (p.work) hipLaunchKernelGGL(explored_cap_slab_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
-        else hipLaunchKernelGGL(explored_cap_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+        return launch_lds_or_slab(explored_cap_kernel, explored_cap_slab_kernel, p.work, (p.n + 63) / 64, 0, p);
     }
     int run_pair_scores(const PmParams& p) override {
         hipSetDevice(dev);
@@ -2285,16 +2277,12 @@ public:
     int run_pair_mapq(const PmParams& p) override {
         hipSetDevice(dev);
         if (!p.n) return VGK_OK;
-        if (p.work) hipLaunchKernelGGL(pair_mapq_slab_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
-        else hipLaunchKernelGGL(pair_mapq_kernel, dim3((p.n + 63) / 64), dim3(64), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+        return launch_lds_or_slab(pair_mapq_kernel, pair_mapq_slab_kernel, p.work, (p.n + 63) / 64, 0, p);
     }
     int run_minimizer_choose(const MzChooseParams& p, uint32_t blocks) override {
         hipSetDevice(dev);
         if (!blocks) return VGK_OK;
-        if (p.slab) hipLaunchKernelGGL(minimizer_choose_slab_kernel, dim3(blocks), dim3(64), 0, stream, p);
-        else hipLaunchKernelGGL(minimizer_choose_kernel, dim3(blocks), dim3(64), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+        return launch_lds_or_slab(minimizer_choose_kernel, minimizer_choose_slab_kernel, p.slab, blocks, 0, p);
     }
     int run_wfa_mask(const WProb* probs, const uint32_t* src_off, const char* raw, char* seqs, uint32_t n) override {
         hipSetDevice(dev);

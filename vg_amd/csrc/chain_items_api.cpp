@@ -28,7 +28,6 @@ bool jump_of(uint64_t d, uint64_t bsl, double gap_scale, int32_t* out) {
     *out = (int32_t)v;
     return true;
 }
-struct Timed { Backend* be; double* ms; int rc = VGK_OK; Timed(Backend* b, double* m) : be(b), ms(m) { be->watch(0); } int done() { be->watch(1); rc = be->sync(); if (!rc) *ms = be->watch_ms(); return rc; } };
 }  // namespace
 
 extern "C" {
@@ -62,7 +61,7 @@ int vgk_chain_items(vgk_ctx* ctx, const vgk_chain_scheme* scheme, uint32_t n_pro
         n_slots += std::max<uint64_t>(1, std::min<uint64_t>(n, scheme->max_chains));
     }
     const uint64_t n_anchors = anchor_off[n_problems], n_cands = cand_off[n_problems];
-    if (n_anchors > 0xfffffff0ull || n_cands > 0xfffffff0ull) return VGK_ETOOBIG;
+    if (n_anchors > INDEX_MOST || n_cands > INDEX_MOST) return VGK_ETOOBIG;
     if ((n_anchors && !anchors) || (n_cands && !candidates)) return VGK_EINVAL;
     // ---- the problems: limits, anchors in order, the mean base seed length, the bound on what a score can sum to
     std::vector<CiProb> probs(n_problems); std::vector<uint64_t> bsl(n_problems, 0), own_sum(n_problems, 0); std::vector<uint8_t> bad(n_problems, 0);
@@ -120,14 +119,7 @@ int vgk_chain_items(vgk_ctx* ctx, const vgk_chain_scheme* scheme, uint32_t n_pro
         for (uint32_t p = 0; p < n_problems; ++p) { probs[p].slot = slot; slot += std::max<uint64_t>(1, std::min<uint64_t>(probs[p].n, scheme->max_chains)); }
     }
     // ---- the launches' problems: those whose tables fit LDS first, the others over slabs
-    std::vector<uint32_t> ids, large;
-    uint32_t lds_largest = 1, slab_largest = 0;
-    for (uint32_t p = 0; p < n_problems; ++p) {
-        if (probs[p].n <= CI_LDS_MAX) { ids.push_back(p); lds_largest = std::max(lds_largest, probs[p].n); }
-        else { large.push_back(p); slab_largest = std::max(slab_largest, probs[p].n); }
-    }
-    const uint32_t n_lds = (uint32_t)ids.size();
-    ids.insert(ids.end(), large.begin(), large.end());
+    const SlabPlan plan = slab_plan(n_problems, [&](uint32_t p) { return probs[p].n <= CI_LDS_MAX ? ROUTE_LDS : ROUTE_SLAB; }, [&](uint32_t p) { return probs[p].n; });
 
     std::lock_guard<std::mutex> lock(ctx->mu);
     Backend* be = ctx->be.get();
@@ -139,7 +131,7 @@ int vgk_chain_items(vgk_ctx* ctx, const vgk_chain_scheme* scheme, uint32_t n_pro
     P.anchors = ctx->scratch_dev<vgk_chain_anchor>(CITEMS_ANCHORS, anchors, sizeof(vgk_chain_anchor) * n_anchors);
     P.cands = ctx->scratch_dev<vgk_chain_candidate>(CITEMS_CANDS, candidates, sizeof(vgk_chain_candidate) * n_cands);
     P.jump = ctx->scratch_dev<int32_t>(CITEMS_JUMP, jump.data(), sizeof(int32_t) * jump.size());
-    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(CITEMS_IDS, ids.data(), sizeof(uint32_t) * ids.size());
+    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(CITEMS_IDS, plan.ids.data(), sizeof(uint32_t) * plan.ids.size());
     P.indel = (uint32_t*)ctx->ensure_scratch(CITEMS_INDEL, sizeof(uint32_t) * std::max<uint64_t>(n_cands, 4));
     P.count = (uint32_t*)ctx->ensure_scratch(CITEMS_COUNT, sizeof(uint32_t) * (n_anchors + 1));
     uint32_t* d_first = (uint32_t*)ctx->ensure_scratch(CITEMS_FIRST, sizeof(uint32_t) * (n_anchors + 1));
@@ -156,15 +148,15 @@ int vgk_chain_items(vgk_ctx* ctx, const vgk_chain_scheme* scheme, uint32_t n_pro
     P.rec_left = (uint32_t*)ctx->ensure_scratch(CITEMS_REC_LEFT, sizeof(uint32_t) * (n_anchors + 1));
     if (!P.probs || !P.cand_off || !P.anchors || !P.cands || !P.jump || !d_ids || !P.indel || !P.count || !d_first || !P.cursor || !P.grouped || !P.flags || !P.t_score || !P.t_source
         || !P.chains || !P.n_chains || !P.items || !P.rec_right || !P.rec_left) return VGK_ENOMEM;
-    uint32_t slab_blocks = 0; char* slab = nullptr;
-    if (!large.empty()) {
-        uint64_t np = 1; while (np < slab_largest) np <<= 1;
-        P.slab_n = slab_largest; P.slab_np = (uint32_t)np; P.slab_stride = ci_slab_bytes(slab_largest, np);
-        slab_blocks = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(large.size(), 512), std::max<uint64_t>(1, (1ull << 30) / P.slab_stride));
-        slab = (char*)ctx->ensure_scratch(CITEMS_SLAB, P.slab_stride * slab_blocks);
+    uint32_t blocks = 0; char* slab = nullptr;
+    if (plan.n_large) {
+        const uint64_t np = pow2_at_least(plan.slab_largest);
+        P.slab_n = (uint32_t)plan.slab_largest; P.slab_np = (uint32_t)np; P.slab_stride = ci_slab_bytes(plan.slab_largest, np);
+        blocks = slab_blocks(plan.n_large, P.slab_stride);
+        slab = (char*)ctx->ensure_scratch(CITEMS_SLAB, P.slab_stride * blocks);
         if (!slab) return VGK_ENOMEM;
     }
-    P.lds_np = 1; while (P.lds_np < lds_largest) P.lds_np <<= 1;
+    P.lds_np = (uint32_t)pow2_at_least(plan.lds_largest);
     int rc = be->zero(P.count, sizeof(uint32_t) * (n_anchors + 1));
     if (!rc) rc = be->zero(P.cursor, sizeof(uint32_t) * (n_anchors + 1));
     if (!rc) rc = be->zero(P.flags, 16);
@@ -173,6 +165,7 @@ int vgk_chain_items(vgk_ctx* ctx, const vgk_chain_scheme* scheme, uint32_t n_pro
     if (!rc) rc = be->zero(P.rec_right, sizeof(uint32_t) * (n_anchors + 1));
     if (!rc) rc = be->zero(P.rec_left, sizeof(uint32_t) * (n_anchors + 1));
     if (rc) return rc;
+    for (int k = 0; k < 3; ++k) ctx->chain_items_ms[k] = 0;
     // ---- legality and grouping
     {
         Timed t(be, &ctx->chain_items_ms[0]);
@@ -189,10 +182,7 @@ int vgk_chain_items(vgk_ctx* ctx, const vgk_chain_scheme* scheme, uint32_t n_pro
     for (int stage = 0; stage < 2; ++stage) {
         Timed t(be, &ctx->chain_items_ms[1 + stage]);
         const int what = stage ? CI_RUN_TRACE : CI_RUN_DP;
-        CiParams L = P;
-        L.ids = d_ids; L.n = n_lds; L.slab = nullptr;
-        rc = be->run_chain_items(L, what, n_lds);
-        if (!rc && !large.empty()) { L.ids = d_ids + n_lds; L.n = (uint32_t)large.size(); L.slab = slab; rc = be->run_chain_items(L, what, slab_blocks); }
+        rc = launch_split(P, d_ids, plan, slab, blocks, [&](const CiParams& L, uint32_t grid) { return be->run_chain_items(L, what, grid); });
         const int rs = t.done();
         if (rc || rs) return rc ? rc : rs;
     }

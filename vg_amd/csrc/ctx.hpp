@@ -4,7 +4,34 @@
 #include <mutex>
 #include <vector>
 #include "backend.hpp"
+#include "launch_split.hpp"
 #include "scratch_slots.hpp"
+
+// the stopwatch around a group of launches: done() waits for them and adds their device time to *ms (a call zeroes its figures first)
+struct Timed {
+    vgk::Backend* be; double* ms;
+    Timed(vgk::Backend* b, double* m) : be(b), ms(m) { be->watch(0); }
+    int done() { be->watch(1); const int rc = be->sync(); if (!rc) *ms += be->watch_ms(); return rc; }
+};
+
+// The two launches of a plan (launch_split.hpp) over its ids in HBM, P by value and without a slab: the items d_ids[0, n_lds) first, then, when there
+// are large ones, d_ids[n_lds, n_lds + n_large) with the slab.  An empty first launch is not sent to the backend.  *made, when given, grows by the
+// launches sent.  A lane per item, launch(P): the large items' slices lie in `work` at work_off[j].
+template <class Params, class Launch>
+int launch_split(Params P, const uint32_t* d_ids, const vgk::LaunchSplit& plan, uint32_t* work, const uint64_t* work_off, Launch launch, uint32_t* made = nullptr) {
+    int rc = VGK_OK;
+    if (plan.n_lds) { P.ids = d_ids; P.n = plan.n_lds; rc = launch(P); if (made) ++*made; }
+    if (!rc && plan.n_large) { P.ids = d_ids + plan.n_lds; P.n = plan.n_large; P.work = work; P.work_off = work_off; rc = launch(P); if (made) ++*made; }
+    return rc;
+}
+// A wavefront or workgroup per item, launch(P, blocks): a block for each of the first launch's items, slab_blocks blocks with a slab each for the second.
+template <class Params, class Launch>
+int launch_split(Params P, const uint32_t* d_ids, const vgk::LaunchSplit& plan, char* slab, uint32_t slab_blocks, Launch launch, uint32_t* made = nullptr) {
+    int rc = VGK_OK;
+    if (plan.n_lds) { P.ids = d_ids; P.n = plan.n_lds; rc = launch(P, plan.n_lds); if (made) ++*made; }
+    if (!rc && plan.n_large) { P.ids = d_ids + plan.n_lds; P.n = plan.n_large; P.slab = slab; rc = launch(P, slab_blocks); if (made) ++*made; }
+    return rc;
+}
 
 // page-locked host staging kept on the context between calls: uninitialised, no page faults, full-rate DMA in both directions
 template <class T> struct PinnedBuf {
@@ -111,6 +138,13 @@ struct vgk_ctx {
     uint64_t read_mapq_reads[3] = {0, 0, 0};   // reads of the last vgk_read_mapq: swept in LDS | over the slab | refused by the checks
     bool mapq_tables = false;      // phred_to_prob and prob_for_at_least_one are in READMAPQ_TABLES
     int ensure_mapq_tables();      // ... put there once per context (read_mapq_api.cpp; callers hold `mu`)
+    // The explored-minimizer sweep of vgk_read_mapq and of vgk_pair_mapq's mates, staged in the READMAPQ_* slots (read_mapq_api.cpp).  H: the host's
+    // view of the n_reads reads.  Every read gets validate's verdict and, when `sweep`, its explored minimizers counted; the slice plan follows
+    // (VGK_ETOOBIG before anything is allocated); then `lock` is taken unless the caller holds it already, the tables are ensured, and min_off,
+    // read_off, status, ids, work_off and — when `sweep` — mins, regions, explored and qual go up.  s->P has all of these and the tables; the
+    // caller adds what its kernel reads besides and launches.  *s lives until those launches are waited for.
+    struct MapqSweep { vgk::MqParams P{}; vgk::SlicePlan plan; std::vector<int32_t> status; const uint32_t* d_ids = nullptr; uint32_t* d_work = nullptr; const uint64_t* d_work_off = nullptr; };
+    int stage_mapq_sweep(const vgk::MqParams& H, bool sweep, int32_t (*validate)(const vgk::MqParams&, uint32_t), std::unique_lock<std::mutex>& lock, MapqSweep* s);
     double pair_mapq_ms[2] = {0, 0};   // last vgk_pair_mapq: the mates' sweep | the score and pair kernels
     uint32_t pair_mapq_launches[2] = {0, 0};   // kernels the last vgk_pair_mapq launched: the mates' sweep | scores and pairs
     uint64_t pair_mapq_pairs[3] = {0, 0, 0};   // pairs of the last vgk_pair_mapq: in LDS | over the slab | refused by the checks

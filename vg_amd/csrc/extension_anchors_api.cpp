@@ -15,11 +15,6 @@
 
 using namespace vgk;
 
-namespace {
-struct Timed { Backend* be; double* ms; int rc = VGK_OK; Timed(Backend* b, double* m) : be(b), ms(m) { be->watch(0); } int done() { be->watch(1); rc = be->sync(); if (!rc) *ms = be->watch_ms(); return rc; } };
-uint32_t pow2_at_least(uint64_t n) { uint32_t np = 1; while (np < n) np <<= 1; return np; }
-}  // namespace
-
 extern "C" {
 
 int vgk_extension_anchors_limits(uint32_t out[4]) {
@@ -54,12 +49,12 @@ int vgk_extension_anchors(vgk_ctx* ctx, const vgk_haplo* index, int32_t match, i
     for (uint32_t p = 0; p < n_problems; ++p) {
         if (seed_off[p + 1] < seed_off[p] || (!from_seeds && ext_off[p + 1] < ext_off[p])) return VGK_EINVAL;
         const uint64_t ns = seed_off[p + 1] - seed_off[p], ne = from_seeds ? 0 : ext_off[p + 1] - ext_off[p];
-        if (ns > 0xfffffff0ull || ne > 0xfffffff0ull) return VGK_ETOOBIG;
+        if (ns > INDEX_MOST || ne > INDEX_MOST) return VGK_ETOOBIG;
         list_bound += ns * ne;                                      // (an extension contains a seed once at most)
-        if (list_bound > 0xfffffff0ull) return VGK_ETOOBIG;
+        if (list_bound > INDEX_MOST) return VGK_ETOOBIG;
     }
     const uint64_t n_seeds = seed_off[n_problems], n_ext = from_seeds ? 0 : ext_off[n_problems];
-    if (n_seeds > 0xfffffff0ull || n_ext > 0xfffffff0ull || n_nodes > 0xfffffff0ull || n_mismatches > 0xfffffff0ull || n_seeds + n_ext > 0xfffffff0ull) return VGK_ETOOBIG;
+    if (n_seeds > INDEX_MOST || n_ext > INDEX_MOST || n_nodes > INDEX_MOST || n_mismatches > INDEX_MOST || n_seeds + n_ext > INDEX_MOST) return VGK_ETOOBIG;
     if ((n_seeds && !seeds) || (n_ext && (!extensions || !nodes)) || (n_mismatches && !mismatches)) return VGK_EINVAL;
     // ---- the problems; the extensions checked
     std::vector<EaProb> probs(n_problems); std::vector<uint32_t> prob_of_ext(std::max<uint64_t>(n_ext, 1)); std::vector<uint8_t> bad(n_problems, 0);
@@ -84,15 +79,11 @@ int vgk_extension_anchors(vgk_ctx* ctx, const vgk_haplo* index, int32_t match, i
     });
     for (uint32_t p = 0; p < n_problems; ++p) if (bad[p]) return VGK_EINVAL;
     // ---- the launches' problems: those whose working arrays fit LDS first, the others over slabs
-    std::vector<uint32_t> ids, large;
-    uint64_t lds_largest = 1, slab_largest = 1, slab_seeds = 0;
-    for (uint32_t p = 0; p < n_problems; ++p) {
-        const uint64_t m = std::max(probs[p].n_seeds, probs[p].n_ext);
-        if (probs[p].n_seeds <= EA_LDS_SEEDS && probs[p].n_ext <= EA_LDS_EXT) { ids.push_back(p); lds_largest = std::max(lds_largest, m); }
-        else { large.push_back(p); slab_largest = std::max(slab_largest, m); slab_seeds = std::max<uint64_t>(slab_seeds, probs[p].n_seeds); }
-    }
-    const uint32_t n_lds = (uint32_t)ids.size();
-    ids.insert(ids.end(), large.begin(), large.end());
+    const SlabPlan plan = slab_plan(n_problems, [&](uint32_t p) { return probs[p].n_seeds <= EA_LDS_SEEDS && probs[p].n_ext <= EA_LDS_EXT ? ROUTE_LDS : ROUTE_SLAB; },
+                                    [&](uint32_t p) { return std::max(probs[p].n_seeds, probs[p].n_ext); });
+    if (plan.slab_largest > 0x80000000ull) return VGK_ETOOBIG;      // (the sorts' power of two would leave 32 bits)
+    uint64_t slab_seeds = 0;                                       // the slab's second size: the most seeds of a large problem
+    for (uint32_t j = 0; j < plan.n_large; ++j) slab_seeds = std::max<uint64_t>(slab_seeds, probs[plan.large()[j]].n_seeds);
 
     std::lock_guard<std::mutex> lock(ctx->mu);
     Backend* be = ctx->be.get();
@@ -105,7 +96,7 @@ int vgk_extension_anchors(vgk_ctx* ctx, const vgk_haplo* index, int32_t match, i
     P.nodes = ctx->scratch_dev<uint32_t>(EANCH_NODES, nodes, n_ext ? sizeof(uint32_t) * n_nodes : 0);
     P.mism = ctx->scratch_dev<uint32_t>(EANCH_MISM, mismatches, n_ext ? sizeof(uint32_t) * n_mismatches : 0);
     P.prob_of_ext = ctx->scratch_dev<uint32_t>(EANCH_PROB_OF_EXT, prob_of_ext.data(), sizeof(uint32_t) * n_ext);
-    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(EANCH_IDS, ids.data(), sizeof(uint32_t) * ids.size());
+    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(EANCH_IDS, plan.ids.data(), sizeof(uint32_t) * plan.ids.size());
     P.seed_anchor = (vgk_chain_anchor*)ctx->ensure_scratch(EANCH_SEED_ANCHOR, sizeof(vgk_chain_anchor) * (n_seeds + 1));
     P.sorted = (uint32_t*)ctx->ensure_scratch(EANCH_SORTED, sizeof(uint32_t) * (n_seeds + 1));
     P.ext_count = (uint32_t*)ctx->ensure_scratch(EANCH_EXT_COUNT, sizeof(uint32_t) * (n_ext + 1));
@@ -122,24 +113,18 @@ int vgk_extension_anchors(vgk_ctx* ctx, const vgk_haplo* index, int32_t match, i
     P.status = (uint32_t*)ctx->ensure_scratch(EANCH_STATUS, sizeof(uint32_t) * n_problems);
     if (!P.probs || !P.seeds || !P.ext || !P.nodes || !P.mism || !P.prob_of_ext || !d_ids || !P.seed_anchor || !P.sorted || !P.ext_count || !d_first || !P.flags || !P.made || !P.made_origin
         || !P.anchors || !P.origins || !P.rep || !P.n_anchors || !P.n_rep || !P.status) return VGK_ENOMEM;
-    uint32_t slab_blocks = 0; char* slab = nullptr;
-    if (!large.empty()) {
-        P.slab_np = pow2_at_least(slab_largest); P.slab_seeds = (uint32_t)slab_seeds; P.slab_stride = ea_work_bytes(P.slab_np, slab_seeds);
-        slab_blocks = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(large.size(), 512), std::max<uint64_t>(1, (1ull << 30) / P.slab_stride));
-        slab = (char*)ctx->ensure_scratch(EANCH_SLAB, P.slab_stride * slab_blocks);
+    uint32_t blocks = 0; char* slab = nullptr;
+    if (plan.n_large) {
+        P.slab_np = (uint32_t)pow2_at_least(plan.slab_largest); P.slab_seeds = (uint32_t)slab_seeds; P.slab_stride = ea_work_bytes(P.slab_np, slab_seeds);
+        blocks = slab_blocks(plan.n_large, P.slab_stride);
+        slab = (char*)ctx->ensure_scratch(EANCH_SLAB, P.slab_stride * blocks);
         if (!slab) return VGK_ENOMEM;
     }
-    P.lds_np = pow2_at_least(lds_largest);
+    P.lds_np = (uint32_t)pow2_at_least(plan.lds_largest);
     int rc = be->zero(P.flags, 16);
     if (!rc) rc = be->zero(P.ext_count, sizeof(uint32_t) * (n_ext + 1));
     if (rc) return rc;
-    auto per_problem = [&](int what) {
-        EaParams L = P;
-        L.ids = d_ids; L.n = n_lds; L.slab = nullptr;
-        int r = n_lds ? be->run_extension_anchors(L, what, n_lds) : VGK_OK;
-        if (!r && !large.empty()) { L.ids = d_ids + n_lds; L.n = (uint32_t)large.size(); L.slab = slab; r = be->run_extension_anchors(L, what, slab_blocks); }
-        return r;
-    };
+    auto per_problem = [&](int what) { return launch_split(P, d_ids, plan, slab, blocks, [&](const EaParams& L, uint32_t grid) { return be->run_extension_anchors(L, what, grid); }); };
     for (int k = 0; k < 3; ++k) ctx->extension_anchors_ms[k] = 0;
     // ---- every seed's anchor, every problem's seeds in diagonal order
     {

@@ -147,7 +147,7 @@ int vgk_minimizer_seeds(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vgk_h
     if (!n) { if (seed_off) seed_off[0] = 0; return VGK_OK; }
     for (uint32_t i = 0; i < n; ++i) if (read_off[i + 1] < read_off[i]) return VGK_EINVAL;
     const uint64_t bytes = read_off[n] - read_off[0];
-    if (bytes > 0xfffffff0ull) return VGK_ETOOBIG;
+    if (bytes > INDEX_MOST) return VGK_ETOOBIG;
     Backend* be = ctx->be.get();
     std::lock_guard<std::mutex> stage(ctx->stage_mu);
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -214,19 +214,19 @@ static int list_on_device(vgk_ctx* ctx, const vgk_minimizer_index* ix, const cha
     *total_out = 0;
     for (uint32_t i = 0; i < n; ++i) if (read_off[i + 1] < read_off[i]) return VGK_EINVAL;
     const uint64_t bytes = read_off[n] - read_off[0];
-    if (bytes > 0xfffffff0ull) return VGK_ETOOBIG;
+    if (bytes > INDEX_MOST) return VGK_ETOOBIG;
     Backend* be = ctx->be.get();
     // a read is cut into stretches of MZ_LIST_WINDOWS windows, a lane each (a 15 kbp read alone would keep one lane busy for 15 000 steps)
     std::vector<MzListItem> items; std::vector<uint64_t> item_first((size_t)n + 1, 0);
     const uint32_t k = ix->dev.k, w = ix->dev.w;
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t L = read_off[i + 1] - read_off[i];
-        if (L > 0xfffffff0ull) return VGK_ETOOBIG;
+        if (L > INDEX_MOST) return VGK_ETOOBIG;
         const uint32_t windows = L >= (uint64_t)k + w - 1 ? (uint32_t)(L - k - w + 2) : 0u;
         for (uint32_t s = 0; s < windows; s += MZ_LIST_WINDOWS) items.push_back(MzListItem{i, s});
         item_first[i + 1] = items.size();
     }
-    if (items.size() > 0xfffffff0ull) return VGK_ETOOBIG;
+    if (items.size() > INDEX_MOST) return VGK_ETOOBIG;
     const uint32_t n_items = (uint32_t)items.size();
     const size_t n1 = (size_t)n + 1, m1 = (size_t)n_items + 1;
     char* d_reads = (char*)ctx->ensure_scratch(MZLIST_READS, bytes + 32);
@@ -289,7 +289,7 @@ static int seeds_of_on_device(vgk_ctx* ctx, const vgk_minimizer_index* ix, const
     if (rc) return rc;
     uint64_t check = 0;
     for (size_t j = 0; j < n_minimizers; ++j) if (take[j]) check += minimizers[j].hits;
-    if (check > 0xfffffff0ull) return VGK_ETOOBIG;
+    if (check > INDEX_MOST) return VGK_ETOOBIG;
     for (size_t j = 0; j < n1; ++j) seed_off[j] = first[j];
     const size_t total = first[n];
     if (written) *written = total;
@@ -307,7 +307,7 @@ int vgk_minimizer_seeds_of(vgk_ctx* ctx, const vgk_minimizer_index* ix, const vg
     if (written) *written = 0;
     seed_off[0] = 0;
     if (!n_minimizers) return VGK_OK;
-    if (n_minimizers > 0xfffffff0ull) return VGK_ETOOBIG;
+    if (n_minimizers > INDEX_MOST) return VGK_ETOOBIG;
     Backend* be = ctx->be.get();
     std::lock_guard<std::mutex> lk(ctx->mu);
     vgk_read_minimizer* d_min = (vgk_read_minimizer*)ctx->ensure_scratch(MZLIST_MINIMIZERS, sizeof(vgk_read_minimizer) * n_minimizers);
@@ -342,40 +342,37 @@ int choose_policy(vgk_ctx* ctx, const vgk_find_seeds_policy* p, MzChoosePolicy* 
 // the choice kernels over a list in HBM (P: everything but ids and the slab): the reads that fit LDS a workgroup each, the others over slabs
 int choose_on_device(vgk_ctx* ctx, MzChooseParams P, const uint64_t* read_off, const uint64_t* minimizer_off, uint32_t n) {
     Backend* be = ctx->be.get();
-    std::vector<uint32_t> ids; std::vector<uint32_t> large;
-    uint64_t max_n = 0, max_L = 0;
+    const auto minimizers_of = [&](uint32_t r) { return minimizer_off[r + 1] - minimizer_off[r]; };
+    const auto bases_of = [&](uint32_t r) { return read_off[r + 1] - read_off[r]; };
     for (uint32_t r = 0; r < n; ++r) {
-        const uint64_t m = minimizer_off[r + 1] - minimizer_off[r], L = read_off[r + 1] - read_off[r];
+        const uint64_t m = minimizers_of(r), L = bases_of(r);
         if (!m) continue;
-        if (m > 0x80000000ull || L > 0xfffffff0ull) return VGK_ETOOBIG;
+        if (m > 0x80000000ull || L > INDEX_MOST) return VGK_ETOOBIG;
         const uint64_t window = mz_choose_window(P.policy, L, P.k);
         if (window && P.k > window) return VGK_EINVAL;                     // (find_seeds' crash_unless(length <= window))
-        if (m <= MZ_CHOOSE_LDS_MAX && L <= MZ_CHOOSE_LDS_BASES) ids.push_back(r);
-        else { large.push_back(r); max_n = std::max(max_n, m); max_L = std::max(max_L, L); }
     }
-    const size_t n_lds = ids.size();
-    ids.insert(ids.end(), large.begin(), large.end());
-    if (ids.empty()) { ctx->minimizer_choose_ms = 0.0; return VGK_OK; }
-    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(MZCHOOSE_IDS, ids.data(), sizeof(uint32_t) * ids.size());
+    const SlabPlan plan = slab_plan(n, [&](uint32_t r) {
+        if (!minimizers_of(r)) return ROUTE_SKIP;                              // nothing to choose from: in neither launch
+        return minimizers_of(r) <= MZ_CHOOSE_LDS_MAX && bases_of(r) <= MZ_CHOOSE_LDS_BASES ? ROUTE_LDS : ROUTE_SLAB;
+    }, minimizers_of);
+    ctx->minimizer_choose_ms = 0.0;
+    if (plan.ids.empty()) return VGK_OK;
+    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(MZCHOOSE_IDS, plan.ids.data(), sizeof(uint32_t) * plan.ids.size());
     if (!d_ids) return VGK_ENOMEM;
-    uint32_t blocks = 0;
-    if (!large.empty()) {
-        uint64_t np = 1; while (np < max_n) np <<= 1;
-        P.slab_np = (uint32_t)np; P.slab_words = (uint32_t)((max_L + 64) / 64);
-        P.slab_stride = 48 * np + 16 * (uint64_t)P.slab_words;             // (minimizer_choose_slab_kernel's layout)
-        blocks = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(large.size(), 512), std::max<uint64_t>(1, (1ull << 30) / P.slab_stride));
-        P.slab = (char*)ctx->ensure_scratch(MZCHOOSE_SLAB, P.slab_stride * blocks);
-        if (!P.slab) return VGK_ENOMEM;
+    uint32_t blocks = 0; char* slab = nullptr;
+    if (plan.n_large) {
+        uint64_t max_L = 0;                                                // the slab's second size: the longest large read
+        for (uint32_t j = 0; j < plan.n_large; ++j) max_L = std::max<uint64_t>(max_L, bases_of(plan.large()[j]));
+        P.slab_np = (uint32_t)pow2_at_least(plan.slab_largest); P.slab_words = (uint32_t)((max_L + 64) / 64);
+        P.slab_stride = mz_choose_slab_bytes(P.slab_np, P.slab_words);
+        blocks = slab_blocks(plan.n_large, P.slab_stride);
+        slab = (char*)ctx->ensure_scratch(MZCHOOSE_SLAB, P.slab_stride * blocks);
+        if (!slab) return VGK_ENOMEM;
     }
-    char* slab = P.slab;
-    be->watch(0);
-    P.ids = d_ids; P.n = (uint32_t)n_lds; P.slab = nullptr;
-    int rc = be->run_minimizer_choose(P, (uint32_t)n_lds);
-    if (!rc && !large.empty()) { P.ids = d_ids + n_lds; P.n = (uint32_t)large.size(); P.slab = slab; rc = be->run_minimizer_choose(P, blocks); }
-    be->watch(1);
-    if (!rc) rc = be->sync();                                              // (ids may go)
-    if (!rc) ctx->minimizer_choose_ms = be->watch_ms();
-    return rc;
+    Timed t(be, &ctx->minimizer_choose_ms);
+    const int rc = launch_split(P, d_ids, plan, slab, blocks, [&](const MzChooseParams& L, uint32_t grid) { return be->run_minimizer_choose(L, grid); });
+    const int rs = t.done();                                               // (ids may go)
+    return rc ? rc : rs;
 }
 }  // namespace
 
@@ -396,7 +393,7 @@ int vgk_minimizer_choose(vgk_ctx* ctx, const vgk_find_seeds_policy* policy, uint
     const uint64_t total = minimizer_off[n], bytes = read_off[n] - read_off[0];
     if (!total) return VGK_OK;
     if (!verdict || (bytes && !reads)) return VGK_EINVAL;
-    if (total > 0xfffffff0ull || bytes > 0xfffffff0ull) return VGK_ETOOBIG;
+    if (total > INDEX_MOST || bytes > INDEX_MOST) return VGK_ETOOBIG;
     Backend* be = ctx->be.get();
     std::lock_guard<std::mutex> lk(ctx->mu);
     MzChooseParams P{};

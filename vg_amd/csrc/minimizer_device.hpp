@@ -369,6 +369,9 @@ struct MzChooseParams {
     const uint32_t* ids; uint32_t n;                                          // the reads of this launch
     char* slab; uint64_t slab_stride; uint32_t slab_np, slab_words;           // the slab route: room per block for slab_np minimizers and bitmaps of slab_words words
 };
+// a block's slab as minimizer_choose_slab_kernel lays it out: three 64-bit arrays of np entries (key, ord, tmp), two bitmaps of `words` 64-bit words
+// (cov, ovl), six 32-bit arrays of np entries (hits, run_hits, start, perm, off, dq)
+VGK_HD uint64_t mz_choose_slab_bytes(uint64_t np, uint64_t words) { return 48 * np + 16 * words; }
 VGK_HD double mz_choose_score(const MzChoosePolicy& Q, uint32_t hits) { return !hits ? 0.0 : (hits <= Q.hard_hit_cap ? Q.tab[hits] : 1.0); }
 // The scores as ranks, for the kernel's sort: the table falls strictly from tab[1] to tab[hard] (the host checks that when it makes it), so a minimizer
 // with 1 <= h <= hard hits has rank 2h, one without hits the last rank 2 hard + 2, and one beyond the hard cap (score 1.0) the rank this finds BY

@@ -15,15 +15,10 @@
 
 using namespace vgk;
 
-namespace {
-struct Timed { Backend* be; double* ms; Timed(Backend* b, double* m) : be(b), ms(m) { be->watch(0); } int done() { be->watch(1); const int rc = be->sync(); if (!rc) *ms += be->watch_ms(); return rc; } };
-constexpr uint64_t RA_MOST = 0xfffffff0ull;
-}  // namespace
-
 // The kernels and the way back, for inputs that lie in HBM already (the caller holds ctx->mu): the explicit call's after its uploads, and the resident
-// form's inside the tail stage (tail_api.cpp), whose sets, tails and ops never left the device.  d_ids: the reads of the LDS launch, then n_large reads
-// for the slab with their slices at d_work_off; nullptr: every read in one launch, a large set's slice by the extensions before it.
-int vgk_read_alignments_run(vgk_ctx* ctx, RaParams& P, const uint32_t* d_ids, uint32_t n_lds, uint32_t n_large, uint32_t* d_work, const uint64_t* d_work_off, uint64_t out_bound,
+// form's inside the tail stage (tail_api.cpp), whose sets, tails and ops never left the device.  d_ids: the reads of `split` (launch_split.hpp), the
+// large sets' slices at d_work_off; nullptr: every read in one launch, a large set's slice by the extensions before it.
+int vgk_read_alignments_run(vgk_ctx* ctx, RaParams& P, const uint32_t* d_ids, const LaunchSplit& split, uint32_t* d_work, const uint64_t* d_work_off, uint64_t out_bound,
                             uint64_t* aln_off, vgk_read_alignment* alignments, size_t cap_alignments, vgk_chain_mapping* mappings, size_t cap_mappings,
                             uint32_t* edits, size_t cap_edits, size_t written[3]) {
     Backend* be = ctx->be.get();
@@ -41,12 +36,8 @@ int vgk_read_alignments_run(vgk_ctx* ctx, RaParams& P, const uint32_t* d_ids, ui
     // ---- which extensions: the small sets in LDS, the large ones over the slab
     {
         Timed t(be, &ctx->read_alignments_ms[0]);
-        RaParams L = P;
-        if (d_ids) {
-            L.ids = d_ids; L.n = n_lds; L.work = nullptr;
-            rc = be->run_read_alignments(L, RA_RUN_SELECT);
-            if (!rc && n_large) { L.ids = d_ids + n_lds; L.n = n_large; L.work = d_work; L.work_off = d_work_off; rc = be->run_read_alignments(L, RA_RUN_SELECT); }
-        } else { L.ids = nullptr; L.n = n; L.work = d_work; L.work_off = nullptr; rc = be->run_read_alignments(L, RA_RUN_SELECT); }
+        if (d_ids) rc = launch_split(P, d_ids, split, d_work, d_work_off, [&](const RaParams& L) { return be->run_read_alignments(L, RA_RUN_SELECT); });
+        else { RaParams L = P; L.ids = nullptr; L.n = n; L.work = d_work; L.work_off = nullptr; rc = be->run_read_alignments(L, RA_RUN_SELECT); }
         const int rs = t.done();                                    // (the staged host arrays may go)
         if (rc || rs) return rc ? rc : rs;
     }
@@ -75,7 +66,7 @@ int vgk_read_alignments_run(vgk_ctx* ctx, RaParams& P, const uint32_t* d_ids, ui
         if ((rc = be->download(&totals[0], d_map_first + n_aln, sizeof(uint32_t))) || (rc = be->download(&totals[1], d_edit_first + n_aln, sizeof(uint32_t)))) return rc;
         unsigned long long wide[2] = {0, 0};                        // the same sums in 64 bits: the prefix sums are 32-bit
         if ((rc = be->download(wide, P.totals, sizeof wide))) return rc;
-        if (wide[0] > RA_MOST || wide[1] > RA_MOST) return VGK_ETOOBIG;
+        if (wide[0] > INDEX_MOST || wide[1] > INDEX_MOST) return VGK_ETOOBIG;
         if (wide[0] != totals[0] || wide[1] != totals[1] || totals[0] > out_bound || totals[1] > out_bound) return VGK_ENODEV;
     }
     if (written) { written[0] = n_aln; written[1] = totals[0]; written[2] = totals[1]; }
@@ -129,13 +120,13 @@ int vgk_read_alignments(vgk_ctx* ctx, const vgk_haplo* index, const vgk_read_ali
     if (!n) return VGK_OK;
     // ---- sizes first, in 64 bits, from the offsets alone
     if (read_off[0] != 0) return VGK_EINVAL;
-    if (n > RA_MOST) return VGK_ETOOBIG;
+    if (n > INDEX_MOST) return VGK_ETOOBIG;
     for (uint32_t r = 0; r < n; ++r) {
         if (read_off[r + 1] < read_off[r]) return VGK_EINVAL;
         if (read_off[r + 1] - read_off[r] > 0x3fffffffull) return VGK_ETOOBIG;
     }
     const uint64_t read_bytes = read_off[n];
-    if (read_bytes > RA_MOST || n_extensions > RA_MOST / 2 || n_nodes > RA_MOST || n_mismatches > RA_MOST || n_tails > RA_MOST - 2 || n_ops > RA_MOST) return VGK_ETOOBIG;
+    if (read_bytes > INDEX_MOST || n_extensions > INDEX_MOST / 2 || n_nodes > INDEX_MOST || n_mismatches > INDEX_MOST || n_tails > INDEX_MOST - 2 || n_ops > INDEX_MOST) return VGK_ETOOBIG;
     if ((read_bytes && !reads) || (n_extensions && (!extensions || !nodes)) || (n_mismatches && !mismatches) || (n_tails && !tails) || (n_ops && !ops)) return VGK_EINVAL;
     std::vector<uint32_t> tail_of(2 * n_extensions + 2);
     if (!ra_tail_table(tails, n_tails, n_extensions, tail_of.data())) return VGK_EINVAL;
@@ -159,16 +150,13 @@ int vgk_read_alignments(vgk_ctx* ctx, const vgk_haplo* index, const vgk_read_ali
         }
         bound[r] = g.full_length ? most : 2 * most + 2;
     });
-    uint64_t out_bound = 0, work_words = 0;
-    std::vector<uint32_t> ids, large; std::vector<uint64_t> work_off;
+    uint64_t out_bound = 0;
     for (uint32_t r = 0; r < n; ++r) {
         out_bound += bound[r];
-        if (out_bound > RA_MOST) return VGK_ETOOBIG;
-        if (status[r] == VGK_OK && results[r].n_ext > RA_LDS_EXT) { large.push_back(r); work_off.push_back(work_words); work_words += ra_work_words(results[r].n_ext); }
-        else ids.push_back(r);
+        if (out_bound > INDEX_MOST) return VGK_ETOOBIG;
     }
-    const uint32_t n_lds = (uint32_t)ids.size();
-    ids.insert(ids.end(), large.begin(), large.end());
+    // (plan.rc is not asked: the select kernel finds a slice by a 64-bit offset, and a slab too large to allocate answers VGK_ENOMEM below)
+    const SlicePlan plan = slice_plan(n, [&](uint32_t r) { return status[r] == VGK_OK && results[r].n_ext > RA_LDS_EXT; }, [&](uint32_t r) { return ra_work_words(results[r].n_ext); });
 
     std::lock_guard<std::mutex> lock(ctx->mu);
     RaParams P{};
@@ -186,11 +174,11 @@ int vgk_read_alignments(vgk_ctx* ctx, const vgk_haplo* index, const vgk_read_ali
     P.ops = ctx->scratch_dev<vgk_op>(READALN_OPS, ops, sizeof(vgk_op) * n_ops);
     P.tail_of = ctx->scratch_dev<uint32_t>(READALN_TAIL_OF, tail_of.data(), sizeof(uint32_t) * 2 * n_extensions);
     P.status = ctx->scratch_dev<int32_t>(READALN_STATUS, status.data(), sizeof(int32_t) * (uint64_t)n);
-    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(READALN_IDS, ids.data(), sizeof(uint32_t) * ids.size());
-    const uint64_t* d_work_off = ctx->scratch_dev<uint64_t>(READALN_WORK_OFF, work_off.data(), sizeof(uint64_t) * work_off.size());
-    uint32_t* d_work = (uint32_t*)ctx->ensure_scratch(READALN_WORK, sizeof(uint32_t) * (work_words + 4));
+    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(READALN_IDS, plan.ids.data(), sizeof(uint32_t) * plan.ids.size());
+    const uint64_t* d_work_off = ctx->scratch_dev<uint64_t>(READALN_WORK_OFF, plan.work_off.data(), sizeof(uint64_t) * plan.work_off.size());
+    uint32_t* d_work = (uint32_t*)ctx->ensure_scratch(READALN_WORK, sizeof(uint32_t) * (plan.work_words + 4));
     if (!P.reads || !P.read_off || !P.res || !P.ext || !P.nodes || !P.mism || !P.tails || !P.ops || !P.tail_of || !P.status || !d_ids || !d_work_off || !d_work) return VGK_ENOMEM;
-    return vgk_read_alignments_run(ctx, P, d_ids, n_lds, (uint32_t)large.size(), d_work, d_work_off, out_bound, aln_off, alignments, cap_alignments, mappings, cap_mappings, edits, cap_edits, written);
+    return vgk_read_alignments_run(ctx, P, d_ids, plan, d_work, d_work_off, out_bound, aln_off, alignments, cap_alignments, mappings, cap_mappings, edits, cap_edits, written);
 } catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }
 
 }  // extern "C"

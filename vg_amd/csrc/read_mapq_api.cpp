@@ -14,11 +14,6 @@
 
 using namespace vgk;
 
-namespace {
-struct Timed { Backend* be; double* ms; Timed(Backend* b, double* m) : be(b), ms(m) { be->watch(0); } int done() { be->watch(1); const int rc = be->sync(); if (!rc) *ms += be->watch_ms(); return rc; } };
-constexpr uint64_t MQ_MOST = 0xfffffff0ull;
-}  // namespace
-
 // once per context: the shim's own expressions, evaluated here (no pow on the device)
 int vgk_ctx::ensure_mapq_tables() {
     if (mapq_tables) return VGK_OK;
@@ -28,6 +23,40 @@ int vgk_ctx::ensure_mapq_tables() {
     const int rt = be->sync();                                      // (tab may go)
     if (rt) return rt;
     mapq_tables = true;
+    return VGK_OK;
+}
+
+// the sweep of vgk_read_mapq and of vgk_pair_mapq's mates up to its launches (ctx.hpp)
+int vgk_ctx::stage_mapq_sweep(const MqParams& H, bool sweep, int32_t (*validate)(const MqParams&, uint32_t), std::unique_lock<std::mutex>& lock, MapqSweep* s) {
+    const uint32_t n = H.n_reads;
+    const uint64_t n_min = H.min_off[n], n_bases = H.read_off[n];
+    s->status.resize(n); std::vector<uint32_t> n_explored(n, 0);
+    parallel_for(n, [&](uint32_t r, unsigned) {
+        s->status[r] = validate(H, r);
+        if (s->status[r] == VGK_OK && sweep) n_explored[r] = mq_count_explored(H, r);
+    });
+    s->plan = slice_plan(n, [&](uint32_t r) { return n_explored[r] > MQ_LDS_EXPLORED; }, [&](uint32_t r) { return mq_work_words(n_explored[r]); });
+    if (s->plan.rc) return s->plan.rc;
+    if (!lock.owns_lock()) lock.lock();
+    const int rt = ensure_mapq_tables();
+    if (rt) return rt;
+    MqParams& P = s->P;
+    P.k = H.k; P.flags = H.flags; P.n_reads = n;
+    P.phred = (const double*)scratch[READMAPQ_TABLES].p; P.events = P.phred + MQ_PHRED_ENTRIES;
+    P.min_off = scratch_dev<uint64_t>(READMAPQ_MIN_OFF, H.min_off, sizeof(uint64_t) * ((uint64_t)n + 1));
+    P.read_off = scratch_dev<uint64_t>(READMAPQ_READ_OFF, H.read_off, sizeof(uint64_t) * ((uint64_t)n + 1));
+    P.status = scratch_dev<int32_t>(READMAPQ_STATUS, s->status.data(), sizeof(int32_t) * (uint64_t)n);
+    s->d_ids = scratch_dev<uint32_t>(READMAPQ_IDS, s->plan.ids.data(), sizeof(uint32_t) * s->plan.ids.size());
+    s->d_work_off = scratch_dev<uint64_t>(READMAPQ_WORK_OFF, s->plan.work_off.data(), sizeof(uint64_t) * s->plan.work_off.size());
+    s->d_work = (uint32_t*)ensure_scratch(READMAPQ_WORK, sizeof(uint32_t) * (s->plan.work_words + 4));
+    if (!P.min_off || !P.read_off || !P.status || !s->d_ids || !s->d_work_off || !s->d_work) return VGK_ENOMEM;
+    if (sweep) {
+        P.mins = scratch_dev<vgk_read_minimizer>(READMAPQ_MINS, H.mins, sizeof(vgk_read_minimizer) * n_min);
+        P.regions = scratch_dev<vgk_minimizer_region>(READMAPQ_REGIONS, H.regions, sizeof(vgk_minimizer_region) * n_min);
+        P.explored = scratch_dev<uint8_t>(READMAPQ_EXPLORED, H.explored, n_min);
+        P.qual = scratch_dev<uint8_t>(READMAPQ_QUAL, H.qual, n_bases);
+        if (!P.mins || !P.regions || !P.explored || !P.qual) return VGK_ENOMEM;
+    }
     return VGK_OK;
 }
 
@@ -58,13 +87,13 @@ int vgk_minimizer_regions(vgk_ctx* ctx, uint32_t k, uint32_t w, const uint64_t* 
     if (!n) return VGK_OK;
     // ---- sizes first, in 64 bits, from the offsets alone; then what vgk_minimizer_choose checks of a list
     if (read_off[0] != 0 || minimizer_off[0] != 0) return VGK_EINVAL;
-    if (n > MQ_MOST) return VGK_ETOOBIG;
+    if (n > INDEX_MOST) return VGK_ETOOBIG;
     for (uint32_t r = 0; r < n; ++r) {
         if (read_off[r + 1] < read_off[r] || minimizer_off[r + 1] < minimizer_off[r]) return VGK_EINVAL;
         if (read_off[r + 1] - read_off[r] > 0x3fffffffull) return VGK_ETOOBIG;
     }
     const uint64_t total = minimizer_off[n];
-    if (total > MQ_MOST) return VGK_ETOOBIG;
+    if (total > INDEX_MOST) return VGK_ETOOBIG;
     if (!total) return VGK_OK;
     if (!minimizers || !regions) return VGK_EINVAL;
     std::vector<uint8_t> bad(n, 0);
@@ -103,73 +132,40 @@ int vgk_read_mapq(vgk_ctx* ctx, const vgk_read_mapq_scheme* scheme, uint32_t n, 
     if (!n) return VGK_OK;
     // ---- sizes first, in 64 bits, from the offsets alone
     if (score_off[0] != 0 || minimizer_off[0] != 0 || read_off[0] != 0) return VGK_EINVAL;
-    if (n > MQ_MOST) return VGK_ETOOBIG;
+    if (n > INDEX_MOST) return VGK_ETOOBIG;
     for (uint32_t r = 0; r < n; ++r) {
         if (score_off[r + 1] < score_off[r] || minimizer_off[r + 1] < minimizer_off[r] || read_off[r + 1] < read_off[r]) return VGK_EINVAL;
         if (read_off[r + 1] - read_off[r] > 0x3fffffffull || minimizer_off[r + 1] - minimizer_off[r] >= MQ_MAX_READ_MINIMIZERS) return VGK_ETOOBIG;
     }
     const uint64_t n_scores = score_off[n], n_min = minimizer_off[n], n_bases = read_off[n];
-    if (n_scores > MQ_MOST || n_min > MQ_MOST || n_bases > MQ_MOST) return VGK_ETOOBIG;
+    if (n_scores > INDEX_MOST || n_min > INDEX_MOST || n_bases > INDEX_MOST) return VGK_ETOOBIG;
     const bool sweep = quality && !(scheme->flags & VGK_READ_MAPQ_NO_EXPLORED_CAP);
     if ((n_scores && !scores) || (sweep && n_min && (!minimizers || !regions || !explored))) return VGK_EINVAL;
-    // ---- every read checked; the reads of the two launches
+    // ---- every read checked, the sweep staged; then what the scores' half reads besides
     MqParams H{};                                                   // the host's view, for the checks
     H.k = scheme->k; H.flags = scheme->flags; H.n_reads = n; H.score_off = score_off; H.unmapped = unmapped; H.min_off = minimizer_off; H.mins = minimizers;
     H.regions = regions; H.explored = explored; H.read_off = read_off; H.qual = quality;
-    std::vector<int32_t> status(n); std::vector<uint32_t> n_explored(n, 0);
-    parallel_for(n, [&](uint32_t r, unsigned) {
-        status[r] = mq_validate_read(H, r);
-        if (status[r] == VGK_OK && sweep) n_explored[r] = mq_count_explored(H, r);
-    });
-    std::vector<uint32_t> ids, large; std::vector<uint64_t> work_off;
-    uint64_t work_words = 0, refused = 0;
-    for (uint32_t r = 0; r < n; ++r) {
-        refused += status[r] != VGK_OK;
-        if (n_explored[r] > MQ_LDS_EXPLORED) { large.push_back(r); work_off.push_back(work_words); work_words += mq_work_words(n_explored[r]); }
-        else ids.push_back(r);
-    }
-    if (work_words > MQ_MOST) return VGK_ETOOBIG;
-    const uint32_t n_lds = (uint32_t)ids.size(), n_large = (uint32_t)large.size();
-    ids.insert(ids.end(), large.begin(), large.end());
-
     Backend* be = ctx->be.get();
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    const int rt = ctx->ensure_mapq_tables();
+    std::unique_lock<std::mutex> lock(ctx->mu, std::defer_lock);
+    vgk_ctx::MapqSweep S;
+    const int rt = ctx->stage_mapq_sweep(H, sweep, mq_validate_read, lock, &S);
     if (rt) return rt;
-    MqParams P{};
-    P.log_base = scheme->log_base; P.score_scale = scheme->score_scale; P.quality_scale = 10.0 / std::log(10.0);
-    P.score_window = scheme->score_window; P.k = scheme->k; P.flags = scheme->flags; P.n_reads = n;
-    P.phred = (const double*)ctx->scratch[READMAPQ_TABLES].p; P.events = P.phred + MQ_PHRED_ENTRIES;
+    MqParams& P = S.P;
+    P.log_base = scheme->log_base; P.score_scale = scheme->score_scale; P.quality_scale = 10.0 / std::log(10.0); P.score_window = scheme->score_window;
     P.score_off = ctx->scratch_dev<uint64_t>(READMAPQ_SCORE_OFF, score_off, sizeof(uint64_t) * ((uint64_t)n + 1));
-    P.min_off = ctx->scratch_dev<uint64_t>(READMAPQ_MIN_OFF, minimizer_off, sizeof(uint64_t) * ((uint64_t)n + 1));
-    P.read_off = ctx->scratch_dev<uint64_t>(READMAPQ_READ_OFF, read_off, sizeof(uint64_t) * ((uint64_t)n + 1));
     P.scores = ctx->scratch_dev<int32_t>(READMAPQ_SCORES, scores, sizeof(int32_t) * n_scores);
-    P.status = ctx->scratch_dev<int32_t>(READMAPQ_STATUS, status.data(), sizeof(int32_t) * (uint64_t)n);
-    const uint32_t* d_ids = ctx->scratch_dev<uint32_t>(READMAPQ_IDS, ids.data(), sizeof(uint32_t) * ids.size());
-    const uint64_t* d_work_off = ctx->scratch_dev<uint64_t>(READMAPQ_WORK_OFF, work_off.data(), sizeof(uint64_t) * work_off.size());
-    uint32_t* d_work = (uint32_t*)ctx->ensure_scratch(READMAPQ_WORK, sizeof(uint32_t) * (work_words + 4));
     P.out = (vgk_read_mapq_result*)ctx->ensure_scratch(READMAPQ_OUT, sizeof(vgk_read_mapq_result) * (uint64_t)n);
-    if (!P.score_off || !P.min_off || !P.read_off || !P.scores || !P.status || !d_ids || !d_work_off || !d_work || !P.out) return VGK_ENOMEM;
+    if (!P.score_off || !P.scores || !P.out) return VGK_ENOMEM;
     if (multiplicity && !(P.mult = ctx->scratch_dev<double>(READMAPQ_MULT, multiplicity, sizeof(double) * n_scores))) return VGK_ENOMEM;
     if (unmapped && !(P.unmapped = ctx->scratch_dev<uint8_t>(READMAPQ_UNMAPPED, unmapped, n))) return VGK_ENOMEM;
-    if (sweep) {
-        P.mins = ctx->scratch_dev<vgk_read_minimizer>(READMAPQ_MINS, minimizers, sizeof(vgk_read_minimizer) * n_min);
-        P.regions = ctx->scratch_dev<vgk_minimizer_region>(READMAPQ_REGIONS, regions, sizeof(vgk_minimizer_region) * n_min);
-        P.explored = ctx->scratch_dev<uint8_t>(READMAPQ_EXPLORED, explored, n_min);
-        P.qual = ctx->scratch_dev<uint8_t>(READMAPQ_QUAL, quality, n_bases);
-        if (!P.mins || !P.regions || !P.explored || !P.qual) return VGK_ENOMEM;
-    }
-    int rc;
     {
         Timed t(be, &ctx->read_mapq_ms[1]);
-        MqParams L = P;
-        L.ids = d_ids; L.n = n_lds; L.work = nullptr; L.work_off = nullptr;
-        rc = be->run_read_mapq(L);
-        if (!rc && n_large) { L.ids = d_ids + n_lds; L.n = n_large; L.work = d_work; L.work_off = d_work_off; rc = be->run_read_mapq(L); }
+        const int rc = launch_split(P, S.d_ids, S.plan, S.d_work, S.d_work_off, [&](const MqParams& L) { return be->run_read_mapq(L); });
         const int rs = t.done();                                    // (the staged host arrays may go)
         if (rc || rs) return rc ? rc : rs;
     }
-    ctx->read_mapq_reads[0] = n_lds - refused; ctx->read_mapq_reads[1] = n_large; ctx->read_mapq_reads[2] = refused;
+    const uint64_t refused = (uint64_t)std::count_if(S.status.begin(), S.status.end(), [](int32_t v) { return v != VGK_OK; });
+    ctx->read_mapq_reads[0] = S.plan.n_lds - refused; ctx->read_mapq_reads[1] = S.plan.n_large; ctx->read_mapq_reads[2] = refused;
     return be->download(out, P.out, sizeof(vgk_read_mapq_result) * (uint64_t)n);
 } catch (const std::bad_alloc&) { return VGK_ENOMEM; } catch (...) { return VGK_EINVAL; }
 

@@ -152,7 +152,7 @@ int vgk_pack_windows_impl(vgk_ctx* ctx, const vgk_dgraph* dg, const char* reads,
                           const vgk_window_problem* problems, uint32_t n, uint32_t ops_per_problem, vgk_batch** out, bool on_device, uint32_t forced_k,
                           const vgk::WinExt* extensions);
 }  // extern "C"
-int vgk_read_alignments_run(vgk_ctx* ctx, vgk::RaParams& P, const uint32_t* d_ids, uint32_t n_lds, uint32_t n_large, uint32_t* d_work, const uint64_t* d_work_off, uint64_t out_bound,
+int vgk_read_alignments_run(vgk_ctx* ctx, vgk::RaParams& P, const uint32_t* d_ids, const vgk::LaunchSplit& split, uint32_t* d_work, const uint64_t* d_work_off, uint64_t out_bound,
                             uint64_t* aln_off, vgk_read_alignment* alignments, size_t cap_alignments, vgk_chain_mapping* mappings, size_t cap_mappings,
                             uint32_t* edits, size_t cap_edits, size_t written[3]);      // read_alignments_api.cpp
 static_assert(offsetof(vgk::GProb, read_off) == 0 && offsetof(vgk::GProb, read_len) == 4 && sizeof(vgk::GProb) % 4 == 0, "RaParams::prob_words reads a GProb's first two words");
@@ -338,7 +338,7 @@ static int tail_stage_impl(vgk_ctx* ctx, const vgk_haplo* index, uint32_t ops_pe
             if (!R.tail_of_out || !d_work) rc = VGK_ENOMEM;
             if (!rc) rc = be->fill(R.tail_of_out, 0xff, sizeof(uint32_t) * 2 * (n_ext + 1));
             if (!rc && nt) rc = be->run_read_alignments(R, RA_RUN_TAILS);
-            if (!rc) rc = vgk_read_alignments_run(ctx, R, nullptr, 0, 0, d_work, nullptr, 0xfffffff0ull, composed->aln_off, composed->alignments, composed->cap_alignments,
+            if (!rc) rc = vgk_read_alignments_run(ctx, R, nullptr, vgk::LaunchSplit{}, d_work, nullptr, 0xfffffff0ull, composed->aln_off, composed->alignments, composed->cap_alignments,
                                                   composed->mappings, composed->cap_mappings, composed->edits, composed->cap_edits, composed->written);
         }
     }
