@@ -107,6 +107,16 @@ tests/emu/read_mapq_san: tests/emu/read_mapq_driver.cpp $(LIB_HDRS)
 	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -DMQ_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 .PHONY: readmapq readmapq_san
 
+# test-only: the serial form of the device rules for a short read's funnel — cluster scores, the three walks, the write-out (read_funnel_device.hpp:
+# rf_walk and the rf_*_one around it) behind one C call each, and the same as a program of its own under the host sanitizers
+readfunnel: tests/emu/libvgamd_readfunnel.so
+tests/emu/libvgamd_readfunnel.so: tests/emu/read_funnel_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -shared -o $@ $<
+readfunnel_san: tests/emu/read_funnel_san
+tests/emu/read_funnel_san: tests/emu/read_funnel_driver.cpp $(LIB_HDRS)
+	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -DFN_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+.PHONY: readfunnel readfunnel_san
+
 # test-only: the serial form of the device rule for a pair's mapping qualities — pair scores, their order, the shared caps (pair_mapq_device.hpp:
 # pm_candidate_score, pm_pair_one; the mates' caps by read_mapq_device.hpp's mq_cap_one) behind one C call, and the same as a program of its own under
 # the host sanitizers

@@ -398,6 +398,104 @@ int vgk_pair_mapq_last_launches(vgk_ctx* ctx, uint64_t pairs[3]);
  * the slab) | the score kernel and the pair kernels (a launch list that is empty launches nothing) */
 int vgk_pair_mapq_last_kernel_launches(vgk_ctx* ctx, uint32_t launches[2]);
 
+/* ---- a short read's funnel on the device: which clusters are extended, which sets are aligned, which alignments win ------------------------------
+ * The three decisions MinimizerMapper::map_from_extensions makes between the stages above (src/minimizer_mapper.cpp:650-1128), for the default
+ * find_supplementaries == false, over flat arrays and with the clusters GIVEN (as vgk_chain_items takes its transitions): no distance index is
+ * read.  The rule is stated serially in vg_amd/csrc/read_funnel_device.hpp (rf_walk and the rf_*_one around it), which the kernels call; the host
+ * shim (vg_amd/host/read_funnel.cpp: vgh_funnel_*) states it in the reference's loop shape and is the checker.
+ *
+ * The walk all three share is process_until_threshold_e (src/minimizer_mapper.hpp:1580-1659) with the escape always false: std::stable_sort by
+ * a comparator; the w >= 2 items tied at the top shuffled; better_or_equal; cutoff = best - threshold; an item fails the threshold when
+ * threshold != 0 && score <= cutoff, unless fewer than `min` items were accepted; any other item is accepted while fewer than `max` were; only
+ * items the step itself accepts count towards min and max.
+ *
+ * vgk_funnel_clusters.  Read r: its length from read_off; its minimizers minimizers[minimizer_off[r] ..) (the k-mer covers offset .. offset + length,
+ * length = policy->k, or the `reserved` field with VGK_FUNNEL_OWN_LENGTH); minimizer_score[] one double per minimizer as score_minimizers makes them
+ * (no logarithm is computed here); its clusters cluster_off[r] .. cluster_off[r + 1]; cluster c's seeds sources[cluster_seed_off[c] ..
+ * cluster_seed_off[c + 1]), each the number WITHIN THE READ of the minimizer the seed came from (Seed::source).  Per cluster (score_cluster, :4738-4770):
+ * score = the scores of the DISTINCT minimizers present, added in ascending minimizer number; covered = the read bases under some present k-mer (a
+ * union); coverage = (double) covered / (double) length; then the walk of :711-832 by coverage descending, then score descending, with
+ * cluster_coverage_threshold, min_extensions, max_extensions and, inside it, the score filter of :746-747 against the padded cutoff of :685-688
+ * (strict <): verdict, rank (position in the walk's order) and better_or_equal (for every item, not only those processed).  Per read:
+ * kept[kept_off[r] .. kept_off[r + 1]) = the clusters extended, in the order extended (the order of cluster_extensions, so the numbering of the
+ * sets below), as indices into the call's flat cluster arrays.
+ *
+ * vgk_funnel_extension_sets.  Read r's sets are results[set_off[r] .. set_off[r + 1]), one vgk_gapless_result per kept cluster in kept order (the
+ * caller ran vgk_gapless_extend with one problem per kept cluster), over `extensions`; set_off must equal kept_off.  Gap open and gap extend are
+ * the context's; a quality-adjusted context: VGK_EUNSUPPORTED.  Per set: estimate = score_extension_group (:5022-5243; a full-length set: its first
+ * extension's score; an empty set: 0; a failed gapless result: 0 and verdict FAILED, never aligned, never counted); the walk of :887-1063 by
+ * estimate descending with extension_set_score_threshold, min_extension_sets, max_alignments: ALIGN, FAIL_SCORE (the threshold), FAIL_MIN_SCORE
+ * (estimate < extension_set_min_score when processed: skipped, counts towards neither min nor max) or FAIL_MAX_ALIGNMENTS; rank, better_or_equal.
+ * Per read: aligned[aligned_off[r] ..) = the sets aligned, in walk order, as indices into `results`; explored[] one byte per minimizer, set when
+ * the minimizer has a seed in a cluster whose set got ALIGN (:1036-1043) — what vgk_read_mapq takes.
+ *
+ * vgk_funnel_winners.  Read r's aligned sets are entries aligned_off[r] .. aligned_off[r + 1] of the aligned list; entry j's alignments, as
+ * vgk_read_alignments ordered them, are aln_score / aln_mappings[aln_off[j] .. aln_off[j + 1]) (score, n_mappings).  Per set the loop of :1025:
+ * alignments are kept while the score is non-zero and at least 0.8 of the set's FIRST alignment's score (compared in double), stopping at the
+ * first that fails.  Nothing kept: one unaligned entry, score 0, pick (0xffffffff, 0xffffffff).  Then the walk of :1095-1128 by score descending,
+ * threshold 0, min 1, max max_multimaps (0: VGK_EINVAL).  scores[score_off[r] ..) = every kept score in walk order, those beyond max_multimaps
+ * included: vgk_read_mapq's `scores`.  reported[] lies on score_off as well: the (aligned-list entry, alignment within it) pair of every score; the
+ * first n_reported[r] = min(count, max_multimaps) of them are the mappings.  unmapped[r] = the first one has no mappings (:1146).
+ *
+ * rng_state (all three calls; uint32 per read, in/out, nullable): the state of the read's std::minstd_rand; 0 = not made yet; made at the first
+ * draw from the read's bytes (`reads`, required with rng_state, otherwise nullable and unread) exactly as find_seeds' sort makes it
+ * (seed = seed * 13 + byte; state = seed mod (2^31 - 1), 1 for 0).  A run of w >= 2 items tied at the top of a walk costs w - 1 draws,
+ * x[rng() % (i + 1)] <-> x[i] for i = 1 .. w - 1 (deterministic_shuffle, src/utility.hpp:721-728); everything else stays in std::stable_sort order.
+ * With NULL nothing is shuffled and ties stay in index order, as vgk_read_alignments leaves them.  Carried through vgk_minimizer_find_seeds' sort
+ * (whose state the caller replays: that entry does not export it), the cluster walk, the set walk and the winner walk, the state models every draw of
+ * a single-end read's life but those inside find_optimal_tail_alignments (:984), which vgk_read_alignments does not make. [PARITY-UNPINNED: the
+ * reference holds no test of these draws; std::sort freedoms the reference leaves open do not arise here: every order is std::stable_sort's.]
+ *
+ * Sizing: kept_cap / aligned_cap / score_cap with written[0] = what the call has; VGK_EOPS when the capacity is short — the offsets, the per-item
+ * outputs and written[] are complete even then (rng_state is advanced by every call that gets that far: size with a copy of it).
+ * Per read, status[r] = VGK_EINVAL with the read's outputs zeroed and nothing kept (the call goes on): a source beyond the read's minimizers, a
+ * k-mer that leaves the read, a read of length 0 that has clusters, a minimizer score that is not finite; for the sets also a kept cluster or an
+ * extension range beyond the arrays, an extension that leaves the read, is empty, or starts before its predecessor.  For the call VGK_EINVAL:
+ * offsets that do not ascend from 0, a threshold that is not finite, unknown flags, set_off that disagrees with kept_off, rng_state without reads;
+ * VGK_ETOOBIG beyond 2^32 - 16 of anything. */
+enum { VGK_FUNNEL_OWN_LENGTH = 1 };       /* policy flags: a minimizer's length is its `reserved` field, as VGK_READ_MAPQ_OWN_LENGTH */
+enum { VGK_FUNNEL_UNDECIDED = 0,          /* (a refused read's items) */
+       VGK_FUNNEL_EXTEND = 1, VGK_FUNNEL_FAIL_COVERAGE = 2, VGK_FUNNEL_FAIL_SCORE = 3, VGK_FUNNEL_FAIL_MAX_EXTENSIONS = 4 };
+enum { VGK_FUNNEL_SET_ALIGN = 1, VGK_FUNNEL_SET_FAIL_SCORE = 2, VGK_FUNNEL_SET_FAIL_MIN_SCORE = 3, VGK_FUNNEL_SET_FAIL_MAX_ALIGNMENTS = 4, VGK_FUNNEL_SET_FAILED = 5 };
+typedef struct vgk_funnel_policy {        /* MinimizerMapper's fields of the same names; giraffe's defaults in brackets */
+    double   cluster_score_threshold;     /* [50] */
+    double   pad_cluster_score_threshold; /* [20] */
+    double   cluster_coverage_threshold;  /* [0.3] */
+    double   extension_set_score_threshold;   /* [20] */
+    int32_t  extension_set_min_score;     /* [20] */
+    uint32_t min_extensions, max_extensions;  /* [2] [800] */
+    uint32_t min_extension_sets, max_alignments;  /* [2] [8] */
+    uint32_t max_multimaps;               /* [1] */
+    uint32_t k;
+    uint32_t flags;                       /* VGK_FUNNEL_* */
+} vgk_funnel_policy;                      /* 64 B */
+typedef struct vgk_funnel_cluster { double score, coverage; uint32_t covered, rank, better_or_equal, verdict; } vgk_funnel_cluster;      /* 32 B */
+typedef struct vgk_funnel_set { int32_t estimate; uint32_t rank, better_or_equal, verdict; } vgk_funnel_set;                           /* 16 B */
+typedef struct vgk_funnel_pick { uint32_t set, alignment; } vgk_funnel_pick;
+int vgk_funnel_clusters(vgk_ctx* ctx, const vgk_funnel_policy* policy, uint32_t n, const char* reads, const uint64_t* read_off,
+                        const uint64_t* minimizer_off, const vgk_read_minimizer* minimizers, const double* minimizer_score,
+                        const uint64_t* cluster_off, const uint64_t* cluster_seed_off, const uint32_t* sources, uint32_t* rng_state,
+                        vgk_funnel_cluster* clusters, int32_t* status /* [n] */, uint64_t* kept_off /* [n + 1] */, uint32_t* kept, size_t kept_cap, size_t written[1]);
+int vgk_funnel_extension_sets(vgk_ctx* ctx, const vgk_funnel_policy* policy, uint32_t n, const char* reads, const uint64_t* read_off,
+                              const uint64_t* set_off, const vgk_gapless_result* results, const vgk_extension* extensions, size_t n_extensions,
+                              const uint64_t* kept_off, const uint32_t* kept, const uint64_t* cluster_seed_off, size_t n_clusters, const uint32_t* sources,
+                              const uint64_t* minimizer_off, uint32_t* rng_state,
+                              vgk_funnel_set* sets, int32_t* status /* [n] */, uint64_t* aligned_off /* [n + 1] */, uint32_t* aligned, size_t aligned_cap,
+                              uint8_t* explored, size_t written[1]);
+int vgk_funnel_winners(vgk_ctx* ctx, const vgk_funnel_policy* policy, uint32_t n, const char* reads, const uint64_t* read_off,
+                       const uint64_t* aligned_off, const uint64_t* aln_off, const int32_t* aln_score, const uint32_t* aln_mappings, uint32_t* rng_state,
+                       uint64_t* score_off /* [n + 1] */, int32_t* scores, vgk_funnel_pick* reported, size_t score_cap,
+                       uint32_t* n_reported /* [n] */, uint8_t* unmapped /* [n] */, size_t written[1]);
+/* What a lane keeps in LDS; items beyond run in a second launch over a slab in HBM.  out[0] = minimizers of a read (a cluster's present bits),
+ * out[1] = bases of a read (a cluster's covered bitmap), out[2] = items of a walk (a read's clusters, sets or kept alignments), out[3] = extensions
+ * of a set (the estimate's chain table).  A lane per cluster or set for the scoring, a lane per read for the walks. */
+int vgk_funnel_limits(uint32_t out[4]);
+/* Device time (ms) of the last vgk_funnel_clusters | vgk_funnel_extension_sets | vgk_funnel_winners call on this context */
+int vgk_funnel_last_ms(vgk_ctx* ctx, double ms[3]);
+/* Reads of the last vgk_funnel_* call by where they ran: every item of theirs in LDS | the walk or some cluster or set of theirs over the slab |
+ * refused by the checks */
+int vgk_funnel_last_launches(vgk_ctx* ctx, uint64_t reads[3]);
+
 /* ---- windows of the resident graph, of any read length: the wide route on the device ------------------------------------------------------
  * vgk_gssw_pack_windows (vgk.h) takes what the packed kernels take: at most 1024 DP rows, scores inside 11 bits; a longer window fails the whole
  * pack with VGK_ETOOLONG.  This one-call entry takes windows of any read length and scoring and answers every problem in its own status, as

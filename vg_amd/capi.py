@@ -259,6 +259,127 @@ def read_mapq_call(fn, head, scheme, score_off, scores, minimizer_off, minimizer
     return rc, out[:n]
 
 
+# vgk_funnel_clusters / vgk_funnel_extension_sets / vgk_funnel_winners (include/vgk_engine.h): a short read's funnel between the stages
+FUNNEL_CLUSTER_DT = np.dtype([("score", "<f8"), ("coverage", "<f8"), ("covered", "<u4"), ("rank", "<u4"), ("better_or_equal", "<u4"), ("verdict", "<u4")])
+FUNNEL_SET_DT = np.dtype([("estimate", "<i4"), ("rank", "<u4"), ("better_or_equal", "<u4"), ("verdict", "<u4")])
+FUNNEL_PICK_DT = np.dtype([("set", "<u4"), ("alignment", "<u4")])
+assert FUNNEL_CLUSTER_DT.itemsize == 32 and FUNNEL_SET_DT.itemsize == 16 and FUNNEL_PICK_DT.itemsize == 8
+FUNNEL_OWN_LENGTH = 1
+FUNNEL_UNDECIDED, FUNNEL_EXTEND, FUNNEL_FAIL_COVERAGE, FUNNEL_FAIL_SCORE, FUNNEL_FAIL_MAX_EXTENSIONS = 0, 1, 2, 3, 4
+FUNNEL_SET_ALIGN, FUNNEL_SET_FAIL_SCORE, FUNNEL_SET_FAIL_MIN_SCORE, FUNNEL_SET_FAIL_MAX_ALIGNMENTS, FUNNEL_SET_FAILED = 1, 2, 3, 4, 5
+FUNNEL_NONE = 0xffffffff
+
+
+class FunnelPolicy(ctypes.Structure):           # vgk_funnel_policy; the defaults are giraffe's
+    _fields_ = [("cluster_score_threshold", ctypes.c_double), ("pad_cluster_score_threshold", ctypes.c_double), ("cluster_coverage_threshold", ctypes.c_double),
+                ("extension_set_score_threshold", ctypes.c_double), ("extension_set_min_score", ctypes.c_int32), ("min_extensions", ctypes.c_uint32),
+                ("max_extensions", ctypes.c_uint32), ("min_extension_sets", ctypes.c_uint32), ("max_alignments", ctypes.c_uint32), ("max_multimaps", ctypes.c_uint32),
+                ("k", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+    @classmethod
+    def giraffe(cls, k, flags=0, **changed):
+        p = cls(50.0, 20.0, 0.3, 20.0, 20, 2, 800, 2, 8, 1, int(k), int(flags))
+        for name, value in changed.items():
+            assert hasattr(p, name), name
+            setattr(p, name, value)
+        return p
+
+
+assert ctypes.sizeof(FunnelPolicy) == 64
+
+
+def _funnel_ptr(a):
+    return a.ctypes.data if a is not None and len(a) else None
+
+
+def _funnel_sized(call, state, cap):
+    """a funnel call at capacity `cap`, or (None) sized first with capacity 0 over a copy of the generator states -> (rc, written, rc of the sizing call)"""
+    if cap is not None:
+        rc, written = call(int(cap), state)
+        return rc, written, None
+    rc0, written = call(0, None if state is None else state.copy())
+    if rc0 not in (VGK_OK, VGK_EOPS):
+        return rc0, written, rc0
+    rc, again = call(written, state)
+    assert rc != VGK_OK or again == written
+    return rc, again, rc0
+
+
+def funnel_clusters_call(fn, head, policy, reads, read_off, minimizer_off, minimizers, minimizer_score, cluster_off, cluster_seed_off, sources, rng_state=None, tail=(), cap=None):
+    """one call with vgk_funnel_clusters' arguments (the engine's, the host shim's vgh_funnel_clusters, the serial lane code's): head / tail = the ctypes values
+    the function takes before `policy` / behind `written`.  rng_state: uint32 per read, updated in place.  cap None: sized with a first call
+    -> (rc, dict(clusters FUNNEL_CLUSTER_DT, status, kept_off, kept, written, sizing_rc))"""
+    off = np.ascontiguousarray(read_off, dtype=np.uint64); moff = np.ascontiguousarray(minimizer_off, dtype=np.uint64); coff = np.ascontiguousarray(cluster_off, dtype=np.uint64)
+    soff = np.ascontiguousarray(cluster_seed_off, dtype=np.uint64); n = len(off) - 1
+    rd = None if reads is None else np.ascontiguousarray(reads, dtype=np.uint8); recs = np.ascontiguousarray(minimizers, dtype=READ_MINIMIZER_DT)
+    ms = np.ascontiguousarray(minimizer_score, dtype=np.float64); src = np.ascontiguousarray(sources, dtype=np.uint32)
+    assert rng_state is None or (rng_state.dtype == np.uint32 and len(rng_state) >= n and rng_state.flags.c_contiguous)
+    clusters = np.zeros(max(len(soff) - 1, 1), dtype=FUNNEL_CLUSTER_DT); status = np.zeros(max(n, 1), dtype=np.int32); kept_off = np.zeros(n + 1, dtype=np.uint64)
+    box = {}
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 13 + [ctypes.c_size_t, ctypes.c_void_p] + [type(t) for t in tail]
+
+    def call(c, state):
+        kept = np.zeros(max(c, 1), dtype=np.uint32); written = (ctypes.c_size_t * 1)()
+        rc = fn(*head, ctypes.byref(policy), n, _funnel_ptr(rd), off.ctypes.data, moff.ctypes.data, _funnel_ptr(recs), _funnel_ptr(ms), coff.ctypes.data, soff.ctypes.data,
+                _funnel_ptr(src), None if state is None else state.ctypes.data, clusters.ctypes.data, status.ctypes.data, kept_off.ctypes.data, kept.ctypes.data if c else None, c, written, *tail)
+        box["kept"] = kept[:c]
+        return rc, int(written[0])
+    rc, written, rc0 = _funnel_sized(call, rng_state, cap)
+    return rc, dict(clusters=clusters[:len(soff) - 1], status=status[:n], kept_off=kept_off, kept=box["kept"][:written] if rc == VGK_OK else box["kept"], written=written, sizing_rc=rc0)
+
+
+def funnel_extension_sets_call(fn, head, policy, reads, read_off, set_off, results, extensions, kept_off, kept, cluster_seed_off, sources, minimizer_off, rng_state=None,
+                               between=(), tail=(), cap=None):
+    """one call with vgk_funnel_extension_sets' arguments; between = what the function takes behind `policy` (the shim and the serial code: gap open, gap extend)
+    -> (rc, dict(sets FUNNEL_SET_DT, status, aligned_off, aligned, explored, written, sizing_rc))"""
+    off = np.ascontiguousarray(read_off, dtype=np.uint64); toff = np.ascontiguousarray(set_off, dtype=np.uint64); koff = np.ascontiguousarray(kept_off, dtype=np.uint64)
+    soff = np.ascontiguousarray(cluster_seed_off, dtype=np.uint64); moff = np.ascontiguousarray(minimizer_off, dtype=np.uint64); n = len(off) - 1
+    rd = None if reads is None else np.ascontiguousarray(reads, dtype=np.uint8); res = np.ascontiguousarray(results, dtype=GAPLESS_RESULT_DT)
+    ext = np.ascontiguousarray(extensions, dtype=EXT_DT); kp = np.ascontiguousarray(kept, dtype=np.uint32); src = np.ascontiguousarray(sources, dtype=np.uint32)
+    assert rng_state is None or (rng_state.dtype == np.uint32 and len(rng_state) >= n and rng_state.flags.c_contiguous)
+    sets = np.zeros(max(len(res), 1), dtype=FUNNEL_SET_DT); status = np.zeros(max(n, 1), dtype=np.int32); aligned_off = np.zeros(n + 1, dtype=np.uint64)
+    explored = np.zeros(max(int(moff[-1]), 1), dtype=np.uint8)
+    box = {}
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_void_p] + [type(t) for t in between] + [ctypes.c_uint32] + [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 \
+        + [ctypes.c_size_t] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p] + [type(t) for t in tail]
+
+    def call(c, state):
+        aligned = np.zeros(max(c, 1), dtype=np.uint32); written = (ctypes.c_size_t * 1)()
+        rc = fn(*head, ctypes.byref(policy), *between, n, _funnel_ptr(rd), off.ctypes.data, toff.ctypes.data, _funnel_ptr(res), _funnel_ptr(ext), len(ext), koff.ctypes.data, _funnel_ptr(kp),
+                soff.ctypes.data, len(soff) - 1, _funnel_ptr(src), moff.ctypes.data, None if state is None else state.ctypes.data, sets.ctypes.data, status.ctypes.data,
+                aligned_off.ctypes.data, aligned.ctypes.data if c else None, c, explored.ctypes.data, written, *tail)
+        box["aligned"] = aligned[:c]
+        return rc, int(written[0])
+    rc, written, rc0 = _funnel_sized(call, rng_state, cap)
+    return rc, dict(sets=sets[:len(res)], status=status[:n], aligned_off=aligned_off, aligned=box["aligned"][:written] if rc == VGK_OK else box["aligned"],
+                    explored=explored[:int(moff[-1])], written=written, sizing_rc=rc0)
+
+
+def funnel_winners_call(fn, head, policy, reads, read_off, aligned_off, aln_off, aln_score, aln_mappings, rng_state=None, tail=(), cap=None):
+    """one call with vgk_funnel_winners' arguments -> (rc, dict(score_off, scores, reported FUNNEL_PICK_DT, n_reported, unmapped, written, sizing_rc))"""
+    off = np.ascontiguousarray(read_off, dtype=np.uint64); aoff = np.ascontiguousarray(aligned_off, dtype=np.uint64); loff = np.ascontiguousarray(aln_off, dtype=np.uint64)
+    n = len(off) - 1
+    rd = None if reads is None else np.ascontiguousarray(reads, dtype=np.uint8); sc = np.ascontiguousarray(aln_score, dtype=np.int32); mp = np.ascontiguousarray(aln_mappings, dtype=np.uint32)
+    assert rng_state is None or (rng_state.dtype == np.uint32 and len(rng_state) >= n and rng_state.flags.c_contiguous)
+    score_off = np.zeros(n + 1, dtype=np.uint64); n_reported = np.zeros(max(n, 1), dtype=np.uint32); unmapped = np.zeros(max(n, 1), dtype=np.uint8)
+    box = {}
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 10 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3 + [type(t) for t in tail]
+
+    def call(c, state):
+        scores = np.zeros(max(c, 1), dtype=np.int32); reported = np.zeros(max(c, 1), dtype=FUNNEL_PICK_DT); written = (ctypes.c_size_t * 1)()
+        rc = fn(*head, ctypes.byref(policy), n, _funnel_ptr(rd), off.ctypes.data, aoff.ctypes.data, loff.ctypes.data, _funnel_ptr(sc), _funnel_ptr(mp),
+                None if state is None else state.ctypes.data, score_off.ctypes.data, scores.ctypes.data if c else None, reported.ctypes.data if c else None, c,
+                n_reported.ctypes.data, unmapped.ctypes.data, written, *tail)
+        box["scores"] = scores[:c]; box["reported"] = reported[:c]
+        return rc, int(written[0])
+    rc, written, rc0 = _funnel_sized(call, rng_state, cap)
+    keep = written if rc == VGK_OK else len(box["scores"])
+    return rc, dict(score_off=score_off, scores=box["scores"][:keep], reported=box["reported"][:keep], n_reported=n_reported[:n], unmapped=unmapped[:n], written=written, sizing_rc=rc0)
+
+
 # vgk_pair_mapq (include/vgk_engine.h): a pair's mapping qualities from its candidate pairings and its mates' explored caps
 PAIR_CANDIDATE_DT = np.dtype([("score", "<i4", (2,)), ("distance", "<i8"), ("aln", "<u4", (2,)), ("better_cluster_count", "<u4"), ("type", "u1"), ("aligned", "u1"), ("reserved", "<u2")])
 PAIR_COUNTS_DT = np.dtype([("unpaired_count", "<u4", (2,)), ("rescued_count", "<u4", (2,))])
@@ -1003,6 +1124,50 @@ class Engine:
         reads = (ctypes.c_uint64 * 3)()
         self.lib.vgk_read_mapq_last_launches.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._check(self.lib.vgk_read_mapq_last_launches(self.h, reads), "vgk_read_mapq_last_launches")
+        return tuple(int(x) for x in reads)
+
+    def funnel_clusters(self, policy, reads, read_off, minimizer_off, minimizers, minimizer_score, cluster_off, cluster_seed_off, sources, rng_state=None, cap=None):
+        """vgk_funnel_clusters (include/vgk_engine.h): per cluster score, covered, coverage, verdict, rank, better_or_equal; per read the clusters extended, in
+        that order.  policy: a FunnelPolicy; rng_state: uint32 per read, updated in place (None: nothing shuffled) -> (rc, dict), rc VGK_OK or VGK_EOPS"""
+        rc, out = funnel_clusters_call(self.lib.vgk_funnel_clusters, (self.h,), policy, reads, read_off, minimizer_off, minimizers, minimizer_score, cluster_off, cluster_seed_off,
+                                       sources, rng_state, cap=cap)
+        if rc != VGK_EOPS:
+            self._check(rc, "vgk_funnel_clusters")
+        return rc, out
+
+    def funnel_extension_sets(self, policy, reads, read_off, set_off, results, extensions, kept_off, kept, cluster_seed_off, sources, minimizer_off, rng_state=None, cap=None):
+        """vgk_funnel_extension_sets: per set estimate, verdict, rank, better_or_equal; per read the sets aligned, in that order, and the explored minimizers"""
+        rc, out = funnel_extension_sets_call(self.lib.vgk_funnel_extension_sets, (self.h,), policy, reads, read_off, set_off, results, extensions, kept_off, kept,
+                                             cluster_seed_off, sources, minimizer_off, rng_state, cap=cap)
+        if rc != VGK_EOPS:
+            self._check(rc, "vgk_funnel_extension_sets")
+        return rc, out
+
+    def funnel_winners(self, policy, reads, read_off, aligned_off, aln_off, aln_score, aln_mappings, rng_state=None, cap=None):
+        """vgk_funnel_winners: per read every kept score in the winner walk's order, where each came from, how many are mappings, and whether the read is unmapped"""
+        rc, out = funnel_winners_call(self.lib.vgk_funnel_winners, (self.h,), policy, reads, read_off, aligned_off, aln_off, aln_score, aln_mappings, rng_state, cap=cap)
+        if rc != VGK_EOPS:
+            self._check(rc, "vgk_funnel_winners")
+        return rc, out
+
+    def funnel_limits(self):
+        """-> what a lane keeps in LDS: (minimizers of a read, bases of a read, items of a walk, extensions of a set)"""
+        out = (ctypes.c_uint32 * 4)()
+        self._check(self.lib.vgk_funnel_limits(out), "vgk_funnel_limits")
+        return tuple(int(x) for x in out)
+
+    def funnel_last_ms(self):
+        """device time of the last funnel_clusters | funnel_extension_sets | funnel_winners call in ms"""
+        ms = (ctypes.c_double * 3)()
+        self.lib.vgk_funnel_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_funnel_last_ms(self.h, ms), "vgk_funnel_last_ms")
+        return tuple(float(x) for x in ms)
+
+    def funnel_last_launches(self):
+        """reads of the last funnel call: (everything in LDS, something over the slab, refused by the checks)"""
+        reads = (ctypes.c_uint64 * 3)()
+        self.lib.vgk_funnel_last_launches.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_funnel_last_launches(self.h, reads), "vgk_funnel_last_launches")
         return tuple(int(x) for x in reads)
 
     def pair_mapq(self, scheme, cand_off, candidates, counts, **rest):

@@ -27,6 +27,7 @@
 #include "read_alignments_device.hpp"
 #include "read_mapq_device.hpp"
 #include "pair_mapq_device.hpp"
+#include "read_funnel_device.hpp"
 
 namespace vgk {
 
@@ -187,6 +188,10 @@ public:
     virtual int   run_explored_caps(const MqParams& p) { (void)p; return VGK_EUNSUPPORTED; }
     virtual int   run_pair_scores(const PmParams& p) { (void)p; return VGK_EUNSUPPORTED; }
     virtual int   run_pair_mapq(const PmParams& p) { (void)p; return VGK_EUNSUPPORTED; }
+    // vgk_funnel_* (read_funnel_device.hpp: rf_item_one), one launch of a pair: a lane per item of p.ids[0 .. p.n) — a cluster, a set or a read, by p.what —
+    // its working words in LDS, or (p.work) in the slab at p.work_off; FN_RUN_GATHER: a lane per read of p.n_reads (rf_gather_one).  Asynchronous on the
+    // main stream.  Optional
+    virtual int   run_funnel(const FnParams& p) { (void)p; return VGK_EUNSUPPORTED; }
     virtual int   run_tail(const TailParams& p, uint32_t threads) = 0;
     virtual int   run_tail_stage(const TStageParams& p, int what) = 0;     // one of the per-item stages of vgk_tail_stage (tail_device.hpp: TS_*)
     virtual int   run_rescue_requests(const RqParams& p, int what) = 0;    // one of the per-pair stages of vgk_rescue_requests (rescue_requests_device.hpp: RQ_*)

@@ -1373,6 +1373,23 @@ __global__ void __launch_bounds__(64) pair_mapq_slab_kernel(const PmParams P) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i < P.n) pm_pair_one(P, P.ids[i], P.work + P.work_off[i]);
 }
+// ---- a short read's funnel (read_funnel_device.hpp: rf_item_one is the rule and the checker).  A lane per cluster or set for the scoring, a lane per read
+// for the walks, by P.what; a cluster's present bits and covered bitmap, a set's chain table, a walk's order lie in LDS, one slice per lane at an odd
+// stride (no two lanes of a wavefront start in one bank), up to the FN_LDS_* limits; the items beyond them come in a launch of their own over slices of
+// a slab.  The gather lays a walk's accepted items out at their prefix sums, a lane per read.
+__global__ void __launch_bounds__(64) funnel_kernel(const FnParams P) {
+    __shared__ uint32_t work[64 * FN_LDS_STRIDE];
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < P.n) rf_item_one(P, P.ids[i], work + threadIdx.x * FN_LDS_STRIDE);
+}
+__global__ void __launch_bounds__(64) funnel_slab_kernel(const FnParams P) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i < P.n) rf_item_one(P, P.ids[i], P.work + P.work_off[i]);
+}
+__global__ void __launch_bounds__(64) funnel_gather_kernel(const FnParams P) {
+    const uint32_t r = blockIdx.x * 64 + threadIdx.x;
+    if (r < P.n_reads) rf_gather_one(P, r);
+}
 __global__ void __launch_bounds__(64) chain_stitch_kernel(const CsParams P, const int what) {
     cs_one(P, what, blockIdx.x * 64 + threadIdx.x);
 }
@@ -2278,6 +2295,16 @@ public:
         hipSetDevice(dev);
         if (!p.n) return VGK_OK;
         return launch_lds_or_slab(pair_mapq_kernel, pair_mapq_slab_kernel, p.work, (p.n + 63) / 64, 0, p);
+    }
+    int run_funnel(const FnParams& p) override {
+        hipSetDevice(dev);
+        if (p.what == FN_RUN_GATHER) {
+            if (!p.n_reads) return VGK_OK;
+            hipLaunchKernelGGL(funnel_gather_kernel, dim3((p.n_reads + 63) / 64), dim3(64), 0, stream, p);
+            return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+        }
+        if (!p.n) return VGK_OK;
+        return launch_lds_or_slab(funnel_kernel, funnel_slab_kernel, p.work, (p.n + 63) / 64, 0, p);
     }
     int run_minimizer_choose(const MzChooseParams& p, uint32_t blocks) override {
         hipSetDevice(dev);

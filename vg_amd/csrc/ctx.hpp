@@ -145,6 +145,8 @@ struct vgk_ctx {
     // caller adds what its kernel reads besides and launches.  *s lives until those launches are waited for.
     struct MapqSweep { vgk::MqParams P{}; vgk::SlicePlan plan; std::vector<int32_t> status; const uint32_t* d_ids = nullptr; uint32_t* d_work = nullptr; const uint64_t* d_work_off = nullptr; };
     int stage_mapq_sweep(const vgk::MqParams& H, bool sweep, int32_t (*validate)(const vgk::MqParams&, uint32_t), std::unique_lock<std::mutex>& lock, MapqSweep* s);
+    double funnel_ms[3] = {0, 0, 0};   // last vgk_funnel_clusters | vgk_funnel_extension_sets | vgk_funnel_winners
+    uint64_t funnel_reads[3] = {0, 0, 0};   // reads of the last vgk_funnel_* call: everything in LDS | something over the slab | refused by the checks
     double pair_mapq_ms[2] = {0, 0};   // last vgk_pair_mapq: the mates' sweep | the score and pair kernels
     uint32_t pair_mapq_launches[2] = {0, 0};   // kernels the last vgk_pair_mapq launched: the mates' sweep | scores and pairs
     uint64_t pair_mapq_pairs[3] = {0, 0, 0};   // pairs of the last vgk_pair_mapq: in LDS | over the slab | refused by the checks

@@ -69,6 +69,14 @@ enum Slot : int {
     // the large pairs' slices and their slab; per candidate its pair score and its place in the order; the 80-byte results
     PAIRMAPQ_CAND_OFF, PAIRMAPQ_CANDS, PAIRMAPQ_COUNTS, PAIRMAPQ_UNP_OFF, PAIRMAPQ_UNP_SCORES, PAIRMAPQ_CAPS, PAIRMAPQ_CAP_STATUS, PAIRMAPQ_STATUS, PAIRMAPQ_IDS,
     PAIRMAPQ_WORK_OFF, PAIRMAPQ_WORK, PAIRMAPQ_SCORE, PAIRMAPQ_ORDER, PAIRMAPQ_OUT,
+    // ---- read_funnel_api.cpp (nothing stays): the reads, their offsets and generators, the checks' verdicts; the minimizers' offsets, list and scores; the
+    // clusters' offsets, seed offsets and sources; the kept clusters, the sets' results and extensions; the aligned sets' offsets, the alignments' offsets,
+    // scores and mapping counts, the winner walk's flat lists; the per-item outputs; a walk's accepted items, their counts and prefix sums, the two laid-out
+    // outputs; the scoring launches' items, slices and slab, and the walk launches'
+    FUNNEL_READS, FUNNEL_READ_OFF, FUNNEL_RNG, FUNNEL_STATUS, FUNNEL_MIN_OFF, FUNNEL_MINS, FUNNEL_MIN_SCORE, FUNNEL_CLUSTER_OFF, FUNNEL_SEED_OFF, FUNNEL_SOURCES,
+    FUNNEL_KEPT_OFF, FUNNEL_KEPT, FUNNEL_RES, FUNNEL_EXT, FUNNEL_ALIGNED_OFF, FUNNEL_ALN_OFF, FUNNEL_ALN_SCORE, FUNNEL_ALN_MAPPINGS, FUNNEL_FLAT_OFF, FUNNEL_FLAT_SCORE,
+    FUNNEL_FLAT_PICK, FUNNEL_SORTED_SCORE, FUNNEL_SORTED_PICK, FUNNEL_CLUSTERS, FUNNEL_SETS, FUNNEL_EXPLORED, FUNNEL_N_REPORTED, FUNNEL_UNMAPPED, FUNNEL_TMP, FUNNEL_COUNT,
+    FUNNEL_FIRST, FUNNEL_OUT0, FUNNEL_OUT1, FUNNEL_IDS, FUNNEL_WORK_OFF, FUNNEL_WORK, FUNNEL_WALK_IDS, FUNNEL_WALK_WORK_OFF, FUNNEL_WALK_WORK,
     // ---- gssw_wide_window_api.cpp (nothing stays): the call's problems, reads and verdicts; a sub-batch's windows, per-node temporaries, sizes, their
     // sums, the order's keys; the results and ops packed for the way back.  The arenas the wide kernels read are the WIDE_* buffers (aliases below)
     WIDEWIN_PROBLEMS, WIDEWIN_READS, WIDEWIN_META, WIDEWIN_SUB, WIDEWIN_STORE, WIDEWIN_NODE_FLAGS, WIDEWIN_SLOT_AT, WIDEWIN_PRED_AT, WIDEWIN_WIN_SLOTS,

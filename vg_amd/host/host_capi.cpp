@@ -1533,3 +1533,127 @@ int vgh_pair_mapq(const vgk_pair_mapq_scheme* scheme, uint32_t n, const uint64_t
     } catch (std::exception& e) { g_last_error = e.what(); return -1; }
 }
 }  // extern "C"
+
+// ---- a short read's funnel (read_funnel.hpp): the checker and CPU baseline of vgk_funnel_clusters / vgk_funnel_extension_sets / vgk_funnel_winners ------
+#include "read_funnel.hpp"
+namespace {
+FunnelPolicy funnel_policy(const vgk_funnel_policy* p) {
+    FunnelPolicy P;
+    P.cluster_score_threshold = p->cluster_score_threshold; P.pad_cluster_score_threshold = p->pad_cluster_score_threshold; P.cluster_coverage_threshold = p->cluster_coverage_threshold;
+    P.extension_set_score_threshold = p->extension_set_score_threshold; P.extension_set_min_score = p->extension_set_min_score;
+    P.min_extensions = p->min_extensions; P.max_extensions = p->max_extensions; P.min_extension_sets = p->min_extension_sets; P.max_alignments = p->max_alignments;
+    P.max_multimaps = p->max_multimaps;
+    return P;
+}
+// a read's generator resumed from its state (0: not made yet), and the state it leaves
+struct FunnelRng {
+    std::unique_ptr<ReadRng> rng;
+    FunnelRng(const char* reads, const uint64_t* read_off, const uint32_t* state, uint32_t r) { if (state) rng.reset(new ReadRng(std::string(reads + read_off[r], reads + read_off[r + 1]), state[r])); }
+    void keep(uint32_t* state, uint32_t r) { if (rng) state[r] = rng->state(); }
+};
+// per-read lists laid out behind each other: off[] and, when they fit, the items; -> VGK_OK or VGK_EOPS
+template <class T, class Put> int funnel_lay_out(uint32_t n, const std::vector<std::vector<T>>& per_read, uint64_t* off, size_t cap, size_t* written, Put put) {
+    off[0] = 0;
+    for (uint32_t r = 0; r < n; ++r) off[r + 1] = off[r] + per_read[r].size();
+    if (written) written[0] = (size_t)off[n];
+    if (off[n] > cap) return VGK_EOPS;
+    for (uint32_t r = 0; r < n; ++r) for (size_t i = 0; i < per_read[r].size(); ++i) put(off[r] + i, per_read[r][i]);
+    return VGK_OK;
+}
+}  // namespace
+extern "C" {
+// vgk_funnel_clusters' arguments less the context; the call's own checks (offsets, thresholds) are the engine's and are not repeated here
+int vgh_funnel_clusters(const vgk_funnel_policy* policy, uint32_t n, const char* reads, const uint64_t* read_off, const uint64_t* minimizer_off, const vgk_read_minimizer* minimizers,
+                        const double* minimizer_score, const uint64_t* cluster_off, const uint64_t* cluster_seed_off, const uint32_t* sources, uint32_t* rng_state,
+                        vgk_funnel_cluster* clusters, int32_t* status, uint64_t* kept_off, uint32_t* kept, size_t kept_cap, size_t* written, int threads) {
+    try {
+        const FunnelPolicy P = funnel_policy(policy);
+        std::vector<std::vector<uint32_t>> kept_of(n);
+        over_reads(n, threads, [&](uint32_t r) {
+            const size_t L = (size_t)(read_off[r + 1] - read_off[r]), M = (size_t)(minimizer_off[r + 1] - minimizer_off[r]);
+            const uint64_t clo = cluster_off[r], chi = cluster_off[r + 1];
+            std::vector<PolicyMinimizer> ms(M); bool ok = !(chi > clo && !L);
+            for (size_t j = 0; j < M; ++j) {
+                const vgk_read_minimizer& m = minimizers[minimizer_off[r] + j];
+                ms[j].key = m.key; ms[j].forward_offset = m.offset; ms[j].length = (policy->flags & VGK_FUNNEL_OWN_LENGTH) ? m.reserved : policy->k; ms[j].hits = m.hits;
+                ms[j].score = minimizer_score[minimizer_off[r] + j];
+                ok = ok && std::isfinite(ms[j].score) && ms[j].forward_offset + ms[j].length <= L;
+            }
+            std::vector<std::vector<size_t>> cl((size_t)(chi - clo));
+            for (uint64_t c = clo; c < chi; ++c) for (uint64_t s = cluster_seed_off[c]; s < cluster_seed_off[c + 1]; ++s) { ok = ok && sources[s] < M; cl[(size_t)(c - clo)].push_back(sources[s]); }
+            status[r] = ok ? VGK_OK : VGK_EINVAL;
+            if (!ok) { for (uint64_t c = clo; c < chi; ++c) clusters[c] = vgk_funnel_cluster{0.0, 0.0, 0u, 0u, 0u, 0u}; return; }
+            FunnelRng g(reads, read_off, rng_state, r);
+            std::vector<FunnelCluster> out;
+            for (size_t c : funnel_clusters(P, L, ms, cl, g.rng.get(), out)) kept_of[r].push_back((uint32_t)(clo + c));
+            g.keep(rng_state, r);
+            for (size_t c = 0; c < out.size(); ++c) clusters[clo + c] = vgk_funnel_cluster{out[c].score, out[c].coverage, out[c].covered, out[c].rank, out[c].better_or_equal, out[c].verdict};
+        });
+        return funnel_lay_out(n, kept_of, kept_off, kept_cap, written, [&](uint64_t at, uint32_t c) { kept[at] = c; });
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+int vgh_funnel_extension_sets(const vgk_funnel_policy* policy, int gap_open, int gap_extend, uint32_t n, const char* reads, const uint64_t* read_off, const uint64_t* set_off,
+                              const vgk_gapless_result* results, const vgk_extension* extensions, size_t n_extensions, const uint64_t* kept_off, const uint32_t* kept,
+                              const uint64_t* cluster_seed_off, size_t n_clusters, const uint32_t* sources, const uint64_t* minimizer_off, uint32_t* rng_state,
+                              vgk_funnel_set* sets, int32_t* status, uint64_t* aligned_off, uint32_t* aligned, size_t aligned_cap, uint8_t* explored, size_t* written, int threads) {
+    try {
+        const FunnelPolicy P = funnel_policy(policy);
+        std::vector<std::vector<uint32_t>> aligned_of(n);
+        over_reads(n, threads, [&](uint32_t r) {
+            const size_t L = (size_t)(read_off[r + 1] - read_off[r]), M = (size_t)(minimizer_off[r + 1] - minimizer_off[r]);
+            const uint64_t lo = set_off[r], hi = set_off[r + 1];
+            std::vector<FunnelSetIn> in((size_t)(hi - lo)); std::vector<std::vector<size_t>> src((size_t)(hi - lo)); bool ok = true;
+            for (uint64_t s = lo; s < hi && ok; ++s) {
+                FunnelSetIn& x = in[(size_t)(s - lo)];
+                const uint32_t c = kept[s];
+                if (c >= n_clusters) { ok = false; break; }
+                for (uint64_t q = cluster_seed_off[c]; q < cluster_seed_off[c + 1]; ++q) { ok = ok && sources[q] < M; src[(size_t)(s - lo)].push_back(sources[q]); }
+                x.sources = &src[(size_t)(s - lo)];
+                const vgk_gapless_result& g = results[s];
+                x.failed = g.status != VGK_OK; x.full_length = g.full_length != 0;
+                if (x.failed) continue;
+                if ((uint64_t)g.ext_begin + g.n_ext > n_extensions) { ok = false; break; }
+                for (uint32_t e = 0; e < g.n_ext; ++e) {
+                    const vgk_extension& v = extensions[g.ext_begin + e];
+                    ok = ok && v.read_begin < v.read_end && v.read_end <= L && !(e && v.read_begin < extensions[g.ext_begin + e - 1].read_begin);
+                    ScoredInterval iv; iv.begin = v.read_begin; iv.end = v.read_end; iv.score = v.score; x.extensions.push_back(iv);
+                }
+            }
+            std::fill(explored + minimizer_off[r], explored + minimizer_off[r + 1], (uint8_t)0);
+            status[r] = ok ? VGK_OK : VGK_EINVAL;
+            if (!ok) { for (uint64_t s = lo; s < hi; ++s) sets[s] = vgk_funnel_set{0, 0u, 0u, 0u}; return; }
+            FunnelRng g(reads, read_off, rng_state, r);
+            std::vector<FunnelSet> out; std::vector<uint8_t> ex(M, 0);
+            for (size_t s : funnel_extension_sets(P, L, in, gap_open, gap_extend, g.rng.get(), out, ex)) aligned_of[r].push_back((uint32_t)(lo + s));
+            g.keep(rng_state, r);
+            std::copy(ex.begin(), ex.end(), explored + minimizer_off[r]);
+            for (size_t s = 0; s < out.size(); ++s) sets[lo + s] = vgk_funnel_set{out[s].estimate, out[s].rank, out[s].better_or_equal, out[s].verdict};
+        });
+        return funnel_lay_out(n, aligned_of, aligned_off, aligned_cap, written, [&](uint64_t at, uint32_t s) { aligned[at] = s; });
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+int vgh_funnel_winners(const vgk_funnel_policy* policy, uint32_t n, const char* reads, const uint64_t* read_off, const uint64_t* aligned_off, const uint64_t* aln_off,
+                       const int32_t* aln_score, const uint32_t* aln_mappings, uint32_t* rng_state, uint64_t* score_off, int32_t* scores, vgk_funnel_pick* reported, size_t score_cap,
+                       uint32_t* n_reported, uint8_t* unmapped, size_t* written, int threads) {
+    try {
+        const FunnelPolicy P = funnel_policy(policy);
+        std::vector<std::vector<std::pair<int32_t, vgk_funnel_pick>>> of(n);
+        over_reads(n, threads, [&](uint32_t r) {
+            std::vector<std::vector<FunnelAlignment>> in;
+            for (uint64_t j = aligned_off[r]; j < aligned_off[r + 1]; ++j) {
+                in.emplace_back();
+                for (uint64_t t = aln_off[j]; t < aln_off[j + 1]; ++t) { FunnelAlignment a; a.score = aln_score[t]; a.n_mappings = aln_mappings[t]; in.back().push_back(a); }
+            }
+            FunnelRng g(reads, read_off, rng_state, r);
+            const FunnelWinners w = funnel_winners(P, in, g.rng.get());
+            g.keep(rng_state, r);
+            for (size_t i = 0; i < w.scores.size(); ++i) {
+                vgk_funnel_pick p; p.set = w.picks[i].set == 0xffffffffu ? 0xffffffffu : (uint32_t)(aligned_off[r] + w.picks[i].set); p.alignment = w.picks[i].alignment;
+                of[r].emplace_back(w.scores[i], p);
+            }
+            n_reported[r] = (uint32_t)w.n_reported; unmapped[r] = w.unmapped ? 1 : 0;
+        });
+        return funnel_lay_out(n, of, score_off, score_cap, written, [&](uint64_t at, const std::pair<int32_t, vgk_funnel_pick>& x) { scores[at] = x.first; reported[at] = x.second; });
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+}  // extern "C"

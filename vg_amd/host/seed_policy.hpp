@@ -51,6 +51,8 @@ void score_minimizers(std::vector<PolicyMinimizer>& minimizers_in_read_order, si
 class ReadRng {
 public:
     explicit ReadRng(std::string seed_sequence) : seed_(std::move(seed_sequence)) {}
+    ReadRng(std::string seed_sequence, uint32_t state) : seed_(std::move(seed_sequence)), started_(state != 0), state_(state ? state : 1) {}      // resumed: 0 = not made yet
+    uint32_t state() const { return started_ ? state_ : 0; }      // what a later ReadRng resumes from
     uint32_t operator()();               // the next number; the generator is made at the first call
     bool started() const { return started_; }
 private:

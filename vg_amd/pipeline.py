@@ -305,8 +305,9 @@ def read_mapq_inputs(seeded, composed):
     """What vgk_read_mapq takes of a read, from the seeding's answer (seed_long_reads(choice="device") / minimizer_find_seeds: minimizer_off, minimizers, take)
     and the composed alignments of the reads (read_alignments / align_stage_device(composed=True)["composed"]): the scores of a read's alignments in their
     order — BEST then SECOND, or the DIRECT ones; an alignment without mappings behind the first is no entry of the reference's `scores` —, the unmapped
-    byte (the first alignment has no mappings), and the explored bytes: on this pipeline a read's cluster is all its seeds, so a minimizer is explored
-    when it was taken and has hits.  -> dict(score_off, scores, unmapped, explored)"""
+    byte (the first alignment has no mappings), and the explored bytes: a minimizer counts as explored when it was taken and has hits — the answer for a
+    read whose one cluster is all its seeds.  A caller that brings real clusters takes scores, unmapped and explored from read_funnel below, which decides per
+    cluster and per extension set as MinimizerMapper::map_from_extensions does.  -> dict(score_off, scores, unmapped, explored)"""
     aln = composed["alignments"]; aln_off = np.ascontiguousarray(composed["aln_off"], dtype=np.int64); n = len(aln_off) - 1
     first = np.zeros(len(aln), dtype=bool); first[aln_off[:-1][aln_off[:-1] < aln_off[1:]]] = True
     counted = first | (aln["n_mappings"] > 0)
@@ -337,6 +338,66 @@ def read_mapq(eng, seeded, composed, read_off, quality, k, w, log_base, flags=0,
     if details is not None:
         details.update(a, per_read=per_read, regions=regions)
     return mapq
+
+
+def minimizer_scores(minimizers, hard_hit_cap=500):
+    """find_minimizers' score per minimizer (score_minimizers of the host shim): 1 + ln(hard_hit_cap) - ln(hits), 1 beyond the hard cap, 0 without hits"""
+    hits = np.asarray(minimizers["hits"], dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        score = np.where(hits <= hard_hit_cap, (1.0 + np.log(float(hard_hit_cap))) - np.log(hits), 1.0)
+    return np.where(hits == 0, 0.0, score)
+
+
+def read_funnel(eng, index, reads, read_off, seeded, cluster_off, cluster_seed_off, cluster_seeds, policy, quality, k, w, log_base, hard_hit_cap=500, rng_state=None,
+                funnel=None, composed_policy=None, flags=0):
+    """A short read's route with its clusters GIVEN, the decisions between the stages made on the device (vgk_funnel_*, include/vgk_engine.h):
+    funnel clusters -> gapless_extend, one problem per kept cluster -> funnel extension sets -> tail stage + read alignments, one "read" per aligned set (the
+    read's bytes gathered per set) -> funnel winners -> read_mapq with the funnel's explored, scores and unmapped in place of read_mapq_inputs' guess.
+    seeded: minimizer_find_seeds' answer (minimizer_off, minimizers, seed_off per minimizer, seeds); cluster c of read r (cluster_off[r] .. cluster_off[r + 1])
+    holds the seeds cluster_seeds[cluster_seed_off[c] .. cluster_seed_off[c + 1]), numbers into seeded["seeds"].  policy: a capi.FunnelPolicy; rng_state:
+    uint32 per read, carried through the three walks (None: nothing shuffled); funnel: who answers the three funnel calls (default: the engine; the tests
+    put the host shim there).  -> dict of every stage's answer; `mapq` = READ_MAPQ_RESULT_DT per read"""
+    funnel = eng if funnel is None else funnel
+    reads = np.ascontiguousarray(reads, dtype=np.uint8); read_off = np.ascontiguousarray(read_off, dtype=np.uint64); n = len(read_off) - 1
+    moff = np.ascontiguousarray(seeded["minimizer_off"], dtype=np.uint64); recs = seeded["minimizers"]
+    cluster_off = np.ascontiguousarray(cluster_off, dtype=np.uint64); cluster_seed_off = np.ascontiguousarray(cluster_seed_off, dtype=np.uint64)
+    cluster_seeds = np.ascontiguousarray(cluster_seeds, dtype=np.int64)
+    minimizer_of_seed = np.repeat(np.arange(len(recs), dtype=np.int64), np.diff(seeded["seed_off"].astype(np.int64)))
+    read_of_minimizer = np.repeat(np.arange(n, dtype=np.int64), np.diff(moff.astype(np.int64)))
+    source_of_seed = minimizer_of_seed - moff.astype(np.int64)[read_of_minimizer[minimizer_of_seed]]                # Seed::source: the minimizer's number within its read
+    sources = source_of_seed[cluster_seeds].astype(np.uint32)
+    read_of_cluster = np.repeat(np.arange(n, dtype=np.int64), np.diff(cluster_off.astype(np.int64)))
+    lengths = np.diff(read_off.astype(np.int64)); seeds_in = np.diff(cluster_seed_off.astype(np.int64))
+
+    def problems(clusters):
+        """a GaplessSet with one problem per cluster of `clusters`: its read's bytes, its seeds"""
+        r = read_of_cluster[clusters]; length = lengths[r]
+        off = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
+        at = np.repeat(read_off.astype(np.int64)[r], length) + (np.arange(int(off[-1])) - np.repeat(off[:-1], length))
+        count = seeds_in[clusters]; soff = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+        which = np.repeat(cluster_seed_off.astype(np.int64)[clusters], count) + (np.arange(int(soff[-1])) - np.repeat(soff[:-1], count))
+        return capi.GaplessSet(reads[at], off, seeded["seeds"][cluster_seeds[which]], soff)
+    out = {}
+    rc, first = funnel.funnel_clusters(policy, reads, read_off, moff, recs, minimizer_scores(recs, hard_hit_cap), cluster_off, cluster_seed_off, sources, rng_state, cap=len(cluster_seed_off) - 1)
+    assert rc == capi.VGK_OK
+    out.update(clusters=first["clusters"], cluster_status=first["status"], kept_off=first["kept_off"], kept=first["kept"], sources=sources)
+    kept = first["kept"].astype(np.int64)
+    res, ext, nodes, mism = eng.gapless_extend(index, problems(kept))
+    res, ext = res.copy(), ext.copy()
+    rc, second = funnel.funnel_extension_sets(policy, reads, read_off, first["kept_off"], res, ext, first["kept_off"], first["kept"], cluster_seed_off, sources, moff, rng_state, cap=len(kept))
+    assert rc == capi.VGK_OK
+    out.update(results=res, extensions=ext, sets=second["sets"], set_status=second["status"], aligned_off=second["aligned_off"], aligned=second["aligned"], explored=second["explored"])
+    stage = align_stage_device(eng, index, problems(kept[second["aligned"].astype(np.int64)]), composed=True, composed_policy=composed_policy or dict(window_length=39))
+    composed = stage["composed"]
+    rc, third = funnel.funnel_winners(policy, reads, read_off, second["aligned_off"], composed["aln_off"], composed["alignments"]["score"], composed["alignments"]["n_mappings"], rng_state,
+                                      cap=len(composed["alignments"]) + n)
+    assert rc == capi.VGK_OK
+    out.update(composed=composed, score_off=third["score_off"], scores=third["scores"], reported=third["reported"], n_reported=third["n_reported"], unmapped=third["unmapped"])
+    regions = eng.minimizer_regions(k, w, read_off, moff, recs)
+    scheme = capi.ReadMapqScheme(float(log_base), 1.0, 0, int(k), int(flags), 0)
+    out["mapq"] = eng.read_mapq(scheme, third["score_off"], third["scores"], moff, recs, regions, second["explored"], read_off, quality, None, third["unmapped"])
+    out["regions"] = regions
+    return out
 
 
 def read_alignments_gaf_view(reads, read_off, composed):
