@@ -117,6 +117,17 @@ tests/emu/read_funnel_san: tests/emu/read_funnel_driver.cpp $(LIB_HDRS)
 	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -DFN_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 .PHONY: readfunnel readfunnel_san
 
+# test-only: the serial composition of the device rule for a chain's links — the checks, the walk, the counts and the write-out
+# (chain_links_device.hpp: cl_check_one, cl_walk_one, cl_count_one, cl_write_one) behind one C call, and the same as a program of its own under the
+# host sanitizers
+chainlinks: tests/emu/libvgamd_chainlinks.so
+tests/emu/libvgamd_chainlinks.so: tests/emu/chain_links_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -shared -o $@ $<
+chainlinks_san: tests/emu/chain_links_san
+tests/emu/chain_links_san: tests/emu/chain_links_driver.cpp $(LIB_HDRS)
+	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -DCL_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+.PHONY: chainlinks chainlinks_san
+
 # test-only: the serial form of the device rule for a pair's mapping qualities — pair scores, their order, the shared caps (pair_mapq_device.hpp:
 # pm_candidate_score, pm_pair_one; the mates' caps by read_mapq_device.hpp's mq_cap_one) behind one C call, and the same as a program of its own under
 # the host sanitizers

@@ -496,6 +496,83 @@ int vgk_funnel_last_ms(vgk_ctx* ctx, double ms[3]);
  * refused by the checks */
 int vgk_funnel_last_launches(vgk_ctx* ctx, uint64_t reads[3]);
 
+/* ---- a chain's links on the device: what find_chain_alignment's walk decides to align, and how ---------------------------------------------------
+ * The first half of MinimizerMapper::find_chain_alignment (src/minimizer_mapper_from_chains.cpp:2576-3292, its decisions only): the step between
+ * vgk_chain_items, which answers with chains of anchor numbers, and the chain stage (vg_amd/host/chain_stage.hpp), which takes a finished link
+ * table and the kept anchors.  No distance index is read: the distances the walk asks for are GIVEN, as vgk_chain_items is given its transitions.
+ * The rule is stated serially in vg_amd/csrc/chain_links_device.hpp (cl_walk_one and cl_slot), which the kernels call; the host shim
+ * (vg_amd/host/chain_links.cpp: vgh_chain_links) states it in the reference's loop shape and is the checker.  No reference unit test names
+ * find_chain_alignment [PARITY-UNPINNED]: the rule is held to a second statement in tests/test_chain_links.py.
+ *
+ * In.  Reads as `reads` / read_off[n_reads + 1].  Anchor sets exactly as vgk_chain_items takes and leaves them: set s's anchors are
+ * anchors[anchor_off[s] .. anchor_off[s + 1]) (read_start and length are read), sites[] one per anchor beside them — graph_start =
+ * (start_node, start_offset), graph_end = (end_node, end_offset), oriented nodes, end_offset past the end within end_node and so at least 1,
+ * bit 0 of flags = Anchor::is_skippable() — and `items` (n_items entries) the flat item array of vgk_chain_items.  Chain p is
+ * {read, anchor_set, item_begin, n_items}: items[item_begin .. item_begin + n_items), anchor numbers within the set, left to right; several chains
+ * may share a read or a set.  Set s's distances are dist[dist_off[s] .. dist_off[s + 1]) as vgk_chain_candidate {from, to, graph_distance}:
+ * graph_distance is what algorithms::get_graph_distance(from, to) answers — end of `from` to start of `to`, NOT the hint distance — strictly
+ * ascending by (from, to); a pair that is absent (or given as UINT32_MAX) is unreachable, SIZE_MAX in the walk.  The walk asks for (here, next) and,
+ * inside the skip loop, for consecutive items (skip_to, skip_to + 1).
+ *
+ * The walk (arithmetic in uint64, the reference's size_t): left tail of here.read_start bases (:2611): at most max_tail_length -> WFA, PREFIX, to =
+ * graph_start(here); at most max_tail_dp_length -> DP; longer -> SOFTCLIP (an insertion without a position, score 0, :2667-2680).  Next anchor
+ * (:2758-2778): items with next.read_start < here.read_end are passed over; none left: the chain ends at here.  Skip past repetitive anchors
+ * (:2786-2863) in the reference's loop shape: strict < against max_skipped_bases, strict > against min_indel_avoid_bases, never past the chain's
+ * last item, += skip_to->length() on both distances.  The link here -> next (:2909-3001, :3044-3051): link_length = next.read_start -
+ * here.read_end, graph_dist as given; both 0 -> EMPTY; else 0 < link_length <= max_chain_connection && graph_dist * link_length <= max_dp_cells ->
+ * WFA, CONNECT, from = graph_end(here) with its offset - 1, to = graph_start(next); else link_length > max_middle_dp_length || graph_dist *
+ * link_length > max_dp_cells -> REFUSED: no link is written, the chain ends at here (kept), VGK_CHAIN_LINKS_CUT is set and the right tail starts at
+ * here.read_end; else -> DP (length 0 allowed: a pure deletion).  Right tail (:3152-3283): read length - here.read_end bases, SUFFIX, from =
+ * graph_end(here) with its offset - 1, classed as the left one.  Kept anchors: `here` at every step.  anchor_score = the sum over them of match *
+ * length, + full_length_bonus for one that starts at read base 0 and for one that ends at the read's end (to_wfa_alignment, :4083-4104).  Plain
+ * scoring only: a quality-adjusted context answers VGK_EUNSUPPORTED.
+ * THE WRAP: graph_dist * link_length, total_graph_distance + cur_graph_distance and the read distance of overlapping neighbours inside the skip loop
+ * wrap in the reference's size_t and wrap here.  With the default max_dp_cells (SIZE_MAX) an unreachable pair whose link has 1 .. max_chain_connection
+ * bases therefore still goes to WFA, as in the reference; with a finite max_dp_cells it is refused.
+ *
+ * Out, dense and in chain order.  Per chain: status, flags, its links links[link_begin .. + n_links) (left tail, connects, right tail, in read
+ * order), its kept anchors kept[kept_begin .. + n_kept) (numbers within the set), left_tail_length, longest_attempted_connection (the longest
+ * WFA-route CONNECT), anchor_score, seq_begin (= seq_off[link_begin]).  Per link: mode (VGK_WFA_*), route, the exclusive end points
+ * (VGK_WFA_NO_NODE / offset 0 where the mode has none), read_begin, length, graph_distance (a tail's own length; UINT32_MAX unreachable), chain.
+ * EMPTY links are written, with length 0: a link stands between any two kept anchors.  seqs (nullable, then seq_off and seq_cap are unread): the
+ * links' bases back to back, link i = seqs[seq_off[i] .. seq_off[i + 1]), as ChainStageInput wants them.
+ *
+ * Room, the caller's: results n_chains; links link_cap (seq_off link_cap + 1), at most the sum of n_items + 1; kept kept_cap, at most the sum of
+ * n_items; seqs seq_cap, at most the sum of the chains' reads' lengths.  VGK_EOPS when a capacity is short: written[0..2] = links, kept anchors,
+ * sequence bytes needed, and nothing else is written.  VGK_ETOOBIG, before anything is allocated, when one of those bounds (summed in 64 bits), the
+ * reads, anchors, items or distances exceed 2^32 - 16.
+ * Per chain VGK_EINVAL, every other field 0, the rest of the call answers: no items; items beyond `items`; an item outside the set; items not
+ * ascending by read_start; a kept anchor that ends past its read; an item whose end_offset is 0; a set whose distances do not ascend strictly or
+ * name anchors outside it.  For the call VGK_EINVAL: offsets that do not ascend from 0, a read or set number outside the batch.  No chains: VGK_OK. */
+enum { VGK_CHAIN_ROUTE_WFA = 0, VGK_CHAIN_ROUTE_DP = 1, VGK_CHAIN_ROUTE_EMPTY = 2, VGK_CHAIN_ROUTE_SOFTCLIP = 3 };
+enum { VGK_CHAIN_SITE_SKIPPABLE = 1 };    /* vgk_chain_site.flags */
+enum { VGK_CHAIN_LINKS_CUT = 1 };         /* vgk_chain_links_result.flags: the chain ends at a refused link */
+typedef struct vgk_chain_site { uint32_t start_node, start_offset, end_node, end_offset, flags; } vgk_chain_site;                 /* 20 B */
+typedef struct vgk_chain_links_scheme {   /* MinimizerMapper's fields of the same names; its defaults in brackets */
+    uint64_t max_chain_connection;        /* [100] */
+    uint64_t max_tail_length;             /* [100] */
+    uint64_t max_middle_dp_length;        /* [2^31 - 1] */
+    uint64_t max_tail_dp_length;          /* [30000] */
+    uint64_t max_dp_cells;                /* [SIZE_MAX] */
+    uint64_t max_skipped_bases;           /* [0] */
+    uint64_t min_indel_avoid_bases;       /* [0] */
+    int32_t  match, full_length_bonus;    /* [1] [5] */
+} vgk_chain_links_scheme;                 /* 64 B */
+typedef struct vgk_chain_problem { uint32_t read, anchor_set, item_begin, n_items; } vgk_chain_problem;
+typedef struct vgk_chain_links_result {
+    int32_t status; uint32_t flags, link_begin, n_links, kept_begin, n_kept, left_tail_length, longest_attempted_connection;
+    int64_t anchor_score; uint64_t seq_begin;
+} vgk_chain_links_result;                 /* 48 B */
+typedef struct vgk_chain_link { uint32_t mode, route, from_node, from_offset, to_node, to_offset, read_begin, length, graph_distance, chain; } vgk_chain_link;   /* 40 B */
+int vgk_chain_links(vgk_ctx* ctx, const vgk_chain_links_scheme* scheme, uint32_t n_reads, const char* reads, const uint64_t* read_off,
+                    uint32_t n_sets, const uint64_t* anchor_off, const vgk_chain_anchor* anchors, const vgk_chain_site* sites,
+                    const uint32_t* items, size_t n_items, const uint64_t* dist_off, const vgk_chain_candidate* dist,
+                    uint32_t n_chains, const vgk_chain_problem* chains,
+                    vgk_chain_links_result* results /* [n_chains] */, vgk_chain_link* links, size_t link_cap, uint32_t* kept, size_t kept_cap,
+                    char* seqs /* nullable */, uint64_t* seq_off /* [link_cap + 1] */, size_t seq_cap, size_t written[3]);
+/* Device time (ms) of the last vgk_chain_links call on this context: checks + walk | counts, prefix sums and write-out | sequences */
+int vgk_chain_links_last_ms(vgk_ctx* ctx, double ms[3]);
+
 /* ---- windows of the resident graph, of any read length: the wide route on the device ------------------------------------------------------
  * vgk_gssw_pack_windows (vgk.h) takes what the packed kernels take: at most 1024 DP rows, scores inside 11 bits; a longer window fails the whole
  * pack with VGK_ETOOLONG.  This one-call entry takes windows of any read length and scoring and answers every problem in its own status, as

@@ -305,6 +305,71 @@ def _funnel_sized(call, state, cap):
     return rc, again, rc0
 
 
+# vgk_chain_links (include/vgk_engine.h): a chain's links — what find_chain_alignment's walk decides to align, and how
+CHAIN_SITE_DT = np.dtype([("start_node", "<u4"), ("start_offset", "<u4"), ("end_node", "<u4"), ("end_offset", "<u4"), ("flags", "<u4")])
+CHAIN_PROBLEM_DT = np.dtype([("read", "<u4"), ("anchor_set", "<u4"), ("item_begin", "<u4"), ("n_items", "<u4")])
+CHAIN_LINKS_RESULT_DT = np.dtype([("status", "<i4"), ("flags", "<u4"), ("link_begin", "<u4"), ("n_links", "<u4"), ("kept_begin", "<u4"), ("n_kept", "<u4"),
+                                  ("left_tail_length", "<u4"), ("longest_attempted_connection", "<u4"), ("anchor_score", "<i8"), ("seq_begin", "<u8")])
+CHAIN_LINK_DT = np.dtype([("mode", "<u4"), ("route", "<u4"), ("from_node", "<u4"), ("from_offset", "<u4"), ("to_node", "<u4"), ("to_offset", "<u4"), ("read_begin", "<u4"),
+                          ("length", "<u4"), ("graph_distance", "<u4"), ("chain", "<u4")])
+assert CHAIN_SITE_DT.itemsize == 20 and CHAIN_PROBLEM_DT.itemsize == 16 and CHAIN_LINKS_RESULT_DT.itemsize == 48 and CHAIN_LINK_DT.itemsize == 40
+CHAIN_ROUTE_WFA, CHAIN_ROUTE_DP, CHAIN_ROUTE_EMPTY, CHAIN_ROUTE_SOFTCLIP = 0, 1, 2, 3
+CHAIN_SITE_SKIPPABLE = 1
+CHAIN_LINKS_CUT = 1
+
+
+class ChainLinksScheme(ctypes.Structure):       # vgk_chain_links_scheme; the defaults are MinimizerMapper's
+    _fields_ = [("max_chain_connection", ctypes.c_uint64), ("max_tail_length", ctypes.c_uint64), ("max_middle_dp_length", ctypes.c_uint64), ("max_tail_dp_length", ctypes.c_uint64),
+                ("max_dp_cells", ctypes.c_uint64), ("max_skipped_bases", ctypes.c_uint64), ("min_indel_avoid_bases", ctypes.c_uint64), ("match", ctypes.c_int32),
+                ("full_length_bonus", ctypes.c_int32)]
+
+    @classmethod
+    def defaults(cls, **changed):
+        p = cls(100, 100, 2 ** 31 - 1, 30000, 2 ** 64 - 1, 0, 0, 1, 5)
+        for name, value in changed.items():
+            assert hasattr(p, name), name
+            setattr(p, name, value)
+        return p
+
+    @classmethod
+    def hifi(cls, **changed):
+        """giraffe's hifi preset where it differs from the defaults"""
+        return cls.defaults(**dict(dict(max_chain_connection=233, max_tail_length=68, max_dp_cells=8000000000, min_indel_avoid_bases=50, max_skipped_bases=1000), **changed))
+
+
+assert ctypes.sizeof(ChainLinksScheme) == 64
+
+
+def chain_links_call(fn, head, scheme, reads, read_off, anchor_off, anchors, sites, items, dist_off, dist, chains, tail=(), caps=None, want_seqs=True):
+    """one call with vgk_chain_links' arguments (the engine's, the host shim's vgh_chain_links, the serial driver's): head / tail = the ctypes values the
+    function takes before `scheme` / behind `written`.  caps None: the bounds the header names (links: sum of n_items + 1, kept: sum of n_items, seqs:
+    sum of the chains' reads' lengths); otherwise (link_cap, kept_cap, seq_cap)
+    -> (rc, dict(results CHAIN_LINKS_RESULT_DT, links CHAIN_LINK_DT, kept, seq_off, seqs, written))"""
+    off = np.ascontiguousarray(read_off, dtype=np.uint64); aoff = np.ascontiguousarray(anchor_off, dtype=np.uint64); doff = np.ascontiguousarray(dist_off, dtype=np.uint64)
+    rd = np.ascontiguousarray(reads, dtype=np.uint8); anc = np.ascontiguousarray(anchors, dtype=CHAIN_ANCHOR_DT); st = np.ascontiguousarray(sites, dtype=CHAIN_SITE_DT)
+    it = np.ascontiguousarray(items, dtype=np.uint32); ds = np.ascontiguousarray(dist, dtype=CHAIN_CANDIDATE_DT); ch = np.ascontiguousarray(chains, dtype=CHAIN_PROBLEM_DT)
+    n_reads, n_sets, n = len(off) - 1, len(aoff) - 1, len(ch)
+    assert len(doff) == len(aoff) and len(st) == len(anc)
+    if caps is None:
+        lens = np.diff(off.astype(np.int64))
+        ok = ch["read"] < n_reads
+        caps = (int(ch["n_items"].astype(np.int64).sum()) + n, int(ch["n_items"].astype(np.int64).sum()), int(lens[ch["read"][ok]].sum()) if n_reads else 0)
+    link_cap, kept_cap, seq_cap = (int(c) for c in caps)
+    results = np.zeros(max(n, 1), dtype=CHAIN_LINKS_RESULT_DT); links = np.zeros(max(link_cap, 1), dtype=CHAIN_LINK_DT); kept = np.zeros(max(kept_cap, 1), dtype=np.uint32)
+    seq_off = np.zeros(link_cap + 1, dtype=np.uint64); seqs = np.zeros(max(seq_cap, 1), dtype=np.uint8); written = (ctypes.c_size_t * 3)()
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + \
+                  [ctypes.c_void_p] * 2 + [ctypes.c_uint32] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                                                      ctypes.c_void_p] + [type(t) for t in tail]
+    rc = fn(*head, ctypes.byref(scheme), n_reads, _funnel_ptr(rd), off.ctypes.data, n_sets, aoff.ctypes.data, _funnel_ptr(anc), _funnel_ptr(st), _funnel_ptr(it), len(it),
+            doff.ctypes.data, _funnel_ptr(ds), n, _funnel_ptr(ch), results.ctypes.data, links.ctypes.data if link_cap else None, link_cap, kept.ctypes.data if kept_cap else None, kept_cap,
+            seqs.ctypes.data if want_seqs else None, seq_off.ctypes.data if want_seqs else None, seq_cap, written, *tail)
+    w = tuple(int(x) for x in written)
+    if rc != VGK_OK:
+        return rc, dict(results=results[:n], written=w)
+    return rc, dict(results=results[:n], links=links[:w[0]], kept=kept[:w[1]], seq_off=seq_off[:w[0] + 1] if want_seqs else None, seqs=seqs[:w[2]] if want_seqs else None, written=w)
+
+
 def funnel_clusters_call(fn, head, policy, reads, read_off, minimizer_off, minimizers, minimizer_score, cluster_off, cluster_seed_off, sources, rng_state=None, tail=(), cap=None):
     """one call with vgk_funnel_clusters' arguments (the engine's, the host shim's vgh_funnel_clusters, the serial lane code's): head / tail = the ctypes values
     the function takes before `policy` / behind `written`.  rng_state: uint32 per read, updated in place.  cap None: sized with a first call
@@ -1169,6 +1234,22 @@ class Engine:
         self.lib.vgk_funnel_last_launches.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._check(self.lib.vgk_funnel_last_launches(self.h, reads), "vgk_funnel_last_launches")
         return tuple(int(x) for x in reads)
+
+    def chain_links(self, scheme, reads, read_off, anchor_off, anchors, sites, items, dist_off, dist, chains, caps=None, want_seqs=True):
+        """vgk_chain_links (include/vgk_engine.h): per chain its links (mode, route, end points, slice of the read, graph distance), its kept anchors and their
+        score.  scheme: a ChainLinksScheme; anchors CHAIN_ANCHOR_DT with sites CHAIN_SITE_DT beside them; items as vgk_chain_items leaves them; dist
+        CHAIN_CANDIDATE_DT ascending by (from, to) per set; chains CHAIN_PROBLEM_DT -> (rc, dict), rc VGK_OK or VGK_EOPS"""
+        rc, out = chain_links_call(self.lib.vgk_chain_links, (self.h,), scheme, reads, read_off, anchor_off, anchors, sites, items, dist_off, dist, chains, caps=caps, want_seqs=want_seqs)
+        if rc != VGK_EOPS:
+            self._check(rc, "vgk_chain_links")
+        return rc, out
+
+    def chain_links_last_ms(self):
+        """device time of the last chain_links call in ms: checks + walk | counts, prefix sums and write-out | sequences"""
+        ms = (ctypes.c_double * 3)()
+        self.lib.vgk_chain_links_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_chain_links_last_ms(self.h, ms), "vgk_chain_links_last_ms")
+        return tuple(float(x) for x in ms)
 
     def pair_mapq(self, scheme, cand_off, candidates, counts, **rest):
         """vgk_pair_mapq (include/vgk_engine.h): per pair both mates' mapping qualities from its candidate pairings — pair scores, their order, the caps both

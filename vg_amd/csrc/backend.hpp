@@ -28,6 +28,7 @@
 #include "read_mapq_device.hpp"
 #include "pair_mapq_device.hpp"
 #include "read_funnel_device.hpp"
+#include "chain_links_device.hpp"
 
 namespace vgk {
 
@@ -192,6 +193,11 @@ public:
     // its working words in LDS, or (p.work) in the slab at p.work_off; FN_RUN_GATHER: a lane per read of p.n_reads (rf_gather_one).  Asynchronous on the
     // main stream.  Optional
     virtual int   run_funnel(const FnParams& p) { (void)p; return VGK_EUNSUPPORTED; }
+    // vgk_chain_links (chain_links_device.hpp), one stage per call: CL_RUN_CHECK a lane per item slot and per distance entry (cl_check_one); CL_RUN_WALK a
+    // lane per chain (cl_walk_one); CL_RUN_COUNT a lane per link slot (cl_count_one) and the three totals added into p.totals in 64 bits; CL_RUN_WRITE a lane
+    // per link slot (cl_write_one), the kept anchors' scores summed per chain into p.res[].anchor_score; CL_RUN_SEQS a wavefront per link of p.n_links: its
+    // bases from the read into p.seqs.  Asynchronous on the main stream.  Optional
+    virtual int   run_chain_links(const ClParams& p, int what) { (void)p; (void)what; return VGK_EUNSUPPORTED; }
     virtual int   run_tail(const TailParams& p, uint32_t threads) = 0;
     virtual int   run_tail_stage(const TStageParams& p, int what) = 0;     // one of the per-item stages of vgk_tail_stage (tail_device.hpp: TS_*)
     virtual int   run_rescue_requests(const RqParams& p, int what) = 0;    // one of the per-pair stages of vgk_rescue_requests (rescue_requests_device.hpp: RQ_*)

@@ -1390,6 +1390,66 @@ __global__ void __launch_bounds__(64) funnel_gather_kernel(const FnParams P) {
     const uint32_t r = blockIdx.x * 64 + threadIdx.x;
     if (r < P.n_reads) rf_gather_one(P, r);
 }
+// ---- a chain's links (chain_links_device.hpp: cl_walk_one and cl_slot are the rule and the checker).  Only the walk is serial, a lane per chain; the
+// checks, the counts and the write-out are a lane per item slot / distance entry / link slot, the sequences a wavefront per link.  No LDS.
+__global__ void __launch_bounds__(256) chain_links_check_kernel(const ClParams P) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < P.n_slots + P.n_dist) cl_check_one(P, i);
+}
+__global__ void __launch_bounds__(64) chain_links_walk_kernel(const ClParams P) {
+    const uint32_t c = blockIdx.x * 64 + threadIdx.x;
+    if (c < P.n_chains) cl_walk_one(P, c);
+}
+// the three counts of every link slot; their totals in 64 bits: summed over the wavefront, one atomic per wavefront and total
+__global__ void __launch_bounds__(256) chain_links_count_kernel(const ClParams P) {
+    const uint32_t ls = blockIdx.x * 256 + threadIdx.x;
+    uint32_t out[3] = {0, 0, 0};
+    if (ls < cl_link_slots(P)) cl_count_one(P, ls, out);
+    unsigned long long t0 = out[0], t1 = out[1], t2 = out[2];
+    for (int d = 32; d > 0; d >>= 1) { t0 += __shfl_xor(t0, d, 64); t1 += __shfl_xor(t1, d, 64); t2 += __shfl_xor(t2, d, 64); }
+    if ((threadIdx.x & 63) == 0) {
+        if (t0) atomicAdd(P.totals + 0, t0);
+        if (t1) atomicAdd(P.totals + 1, t1);
+        if (t2) atomicAdd(P.totals + 2, t2);
+    }
+}
+// the write-out; anchor_score: a segmented sum — a wavefront's lanes of one chain are neighbours, so an inclusive scan that stops at the chain's first
+// lane leaves the chain's share in its last lane of the wavefront, which adds it: one atomic per wavefront per chain (integers: any order, one sum)
+__global__ void __launch_bounds__(256) chain_links_write_kernel(const ClParams P) {
+    const uint32_t ls = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const bool live = ls < cl_link_slots(P);
+    uint32_t chain = 0xffffffffu;
+    long long share = 0;
+    if (live) share = cl_write_one(P, ls, &chain);
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const long long up = __shfl_up(share, d, 64); const uint32_t up_chain = __shfl_up(chain, d, 64);
+        if (lane >= d && up_chain == chain) share += up;
+    }
+    const uint32_t down_chain = __shfl_down(chain, 1, 64);
+    if (live && share != 0 && (lane == 63 || down_chain != chain)) atomicAdd((unsigned long long*)&P.res[chain].anchor_score, (unsigned long long)share);
+}
+// a link's bases from its read: a wavefront per link; dwords where source and destination agree in alignment (bytes up to the first aligned
+// destination and behind the last whole dword), bytes otherwise
+__global__ void __launch_bounds__(256) chain_links_seq_kernel(const ClParams P) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= P.n_links) return;
+    const vgk_chain_link L = P.links[i];
+    const char* src = P.reads + P.read_off[P.chains[L.chain].read] + L.read_begin;
+    char* dst = P.seqs + P.seq_off[i];
+    const uint32_t len = L.length;
+    if ((((uintptr_t)src ^ (uintptr_t)dst) & 3) == 0) {
+        uint32_t head = (uint32_t)((4 - ((uintptr_t)dst & 3)) & 3);
+        if (head > len) head = len;
+        if (lane < head) dst[lane] = src[lane];
+        const uint32_t words = (len - head) / 4;
+        const uint32_t* s4 = (const uint32_t*)(src + head); uint32_t* d4 = (uint32_t*)(dst + head);
+        for (uint32_t k = lane; k < words; k += 64) d4[k] = s4[k];
+        const uint32_t done = head + 4 * words;
+        if (lane < len - done) dst[done + lane] = src[done + lane];
+    } else {
+        for (uint32_t k = lane; k < len; k += 64) dst[k] = src[k];
+    }
+}
 __global__ void __launch_bounds__(64) chain_stitch_kernel(const CsParams P, const int what) {
     cs_one(P, what, blockIdx.x * 64 + threadIdx.x);
 }
@@ -2305,6 +2365,18 @@ public:
         }
         if (!p.n) return VGK_OK;
         return launch_lds_or_slab(funnel_kernel, funnel_slab_kernel, p.work, (p.n + 63) / 64, 0, p);
+    }
+    int run_chain_links(const ClParams& p, int what) override {
+        hipSetDevice(dev);
+        const uint64_t lanes = what == CL_RUN_CHECK ? p.n_slots + p.n_dist : what == CL_RUN_WALK ? p.n_chains : what == CL_RUN_SEQS ? p.n_links : cl_link_slots(p);
+        if (!lanes) return VGK_OK;
+        if (what == CL_RUN_CHECK) hipLaunchKernelGGL(chain_links_check_kernel, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, stream, p);
+        else if (what == CL_RUN_WALK) hipLaunchKernelGGL(chain_links_walk_kernel, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, stream, p);
+        else if (what == CL_RUN_COUNT) hipLaunchKernelGGL(chain_links_count_kernel, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, stream, p);
+        else if (what == CL_RUN_WRITE) hipLaunchKernelGGL(chain_links_write_kernel, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, stream, p);
+        else if (what == CL_RUN_SEQS) hipLaunchKernelGGL(chain_links_seq_kernel, dim3((uint32_t)((lanes + 3) / 4)), dim3(256), 0, stream, p);
+        else return VGK_EINVAL;
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }
     int run_minimizer_choose(const MzChooseParams& p, uint32_t blocks) override {
         hipSetDevice(dev);

@@ -77,6 +77,12 @@ enum Slot : int {
     FUNNEL_KEPT_OFF, FUNNEL_KEPT, FUNNEL_RES, FUNNEL_EXT, FUNNEL_ALIGNED_OFF, FUNNEL_ALN_OFF, FUNNEL_ALN_SCORE, FUNNEL_ALN_MAPPINGS, FUNNEL_FLAT_OFF, FUNNEL_FLAT_SCORE,
     FUNNEL_FLAT_PICK, FUNNEL_SORTED_SCORE, FUNNEL_SORTED_PICK, FUNNEL_CLUSTERS, FUNNEL_SETS, FUNNEL_EXPLORED, FUNNEL_N_REPORTED, FUNNEL_UNMAPPED, FUNNEL_TMP, FUNNEL_COUNT,
     FUNNEL_FIRST, FUNNEL_OUT0, FUNNEL_OUT1, FUNNEL_IDS, FUNNEL_WORK_OFF, FUNNEL_WORK, FUNNEL_WALK_IDS, FUNNEL_WALK_WORK_OFF, FUNNEL_WALK_WORK,
+    // ---- chain_links_api.cpp (nothing stays): the reads and their offsets; the sets' offsets, anchors, sites and the item array; the distances and their
+    // offsets; the chains and their first item slots; a set's verdict, the kept bytes and the route bytes (one block, zeroed together); the three counts per
+    // link slot, their prefix sums, the 64-bit totals; the results, links, kept anchors, sequence offsets and sequences on their way back
+    CHAINLINKS_READS, CHAINLINKS_READ_OFF, CHAINLINKS_ANCHOR_OFF, CHAINLINKS_ANCHORS, CHAINLINKS_SITES, CHAINLINKS_ITEMS, CHAINLINKS_DIST_OFF, CHAINLINKS_DIST,
+    CHAINLINKS_CHAINS, CHAINLINKS_SLOT_OFF, CHAINLINKS_BYTES, CHAINLINKS_COUNT, CHAINLINKS_FIRST, CHAINLINKS_TOTALS, CHAINLINKS_RES, CHAINLINKS_LINKS,
+    CHAINLINKS_KEPT, CHAINLINKS_SEQ_OFF, CHAINLINKS_SEQS,
     // ---- gssw_wide_window_api.cpp (nothing stays): the call's problems, reads and verdicts; a sub-batch's windows, per-node temporaries, sizes, their
     // sums, the order's keys; the results and ops packed for the way back.  The arenas the wide kernels read are the WIDE_* buffers (aliases below)
     WIDEWIN_PROBLEMS, WIDEWIN_READS, WIDEWIN_META, WIDEWIN_SUB, WIDEWIN_STORE, WIDEWIN_NODE_FLAGS, WIDEWIN_SLOT_AT, WIDEWIN_PRED_AT, WIDEWIN_WIN_SLOTS,

@@ -1,5 +1,6 @@
 // chain_stage.cpp — see chain_stage.hpp.
 #include "chain_stage.hpp"
+#include "vgk_engine.h"
 #include <algorithm>
 #include <chrono>
 #include <deque>
@@ -36,22 +37,32 @@ int run_chain_stage(const EngineApi& api, vgk_ctx* ctx, const vgk_haplo* index, 
         p.from_node = in.from_node[i]; p.from_offset = in.from_offset[i]; p.to_node = in.to_node[i]; p.to_offset = in.to_offset[i];
         bases += p.seq_len;
     }
-    std::vector<vgk_wfa_result> results(n);
+    // with routes: the problems WFA gets are the WFA-route links, compacted; wfa_of[i] = link i's number among them (none: NOT_WFA)
+    constexpr uint32_t NOT_WFA = 0xffffffffu;
+    std::vector<uint32_t> wfa_of; std::vector<vgk_wfa_problem> wfa_problems;
+    if (in.route) {
+        wfa_of.assign(n, NOT_WFA);
+        for (uint32_t i = 0; i < n; ++i) if (in.route[i] == VGK_CHAIN_ROUTE_WFA) { wfa_of[i] = (uint32_t)wfa_problems.size(); wfa_problems.push_back(problems[i]); }
+    }
+    const uint32_t n_wfa = in.route ? (uint32_t)wfa_problems.size() : n;
+    const vgk_wfa_problem* to_wfa = in.route ? wfa_problems.data() : problems.data();
+    auto wfa_number = [&](uint32_t i) { return in.route ? wfa_of[i] : i; };
+    std::vector<vgk_wfa_result> results(n_wfa);
     size_t written[2] = {0, 0};
     (void)bases;
     // The chainer knows how far apart two anchors are in the graph: a connect whose sequence differs from that by g bases holds a gap of
     // g bases and costs WFA what a much longer link costs.  The hint puts such links first in the launch, which otherwise ends ~17 ms
     // after the LAST of them happens to be handed out.  It changes the order only.
-    if (in.graph_distance && n && api.wfa_set_cost_hints) {
-        std::vector<uint32_t> hints(n, 0);
+    if (in.graph_distance && n_wfa && api.wfa_set_cost_hints) {
+        std::vector<uint32_t> hints(n_wfa, 0);
         for (uint32_t i = 0; i < n; ++i) {
-            if (in.mode[i] != VGK_WFA_CONNECT) continue;
+            if (in.mode[i] != VGK_WFA_CONNECT || wfa_number(i) == NOT_WFA) continue;
             const int64_t gap = (int64_t)problems[i].seq_len - (int64_t)in.graph_distance[i];
-            hints[i] = (uint32_t)std::min<int64_t>(64 * (gap < 0 ? -gap : gap), 60000);
+            hints[wfa_number(i)] = (uint32_t)std::min<int64_t>(64 * (gap < 0 ? -gap : gap), 60000);
         }
-        api.wfa_set_cost_hints(ctx, hints.data(), n);
+        api.wfa_set_cost_hints(ctx, hints.data(), n_wfa);
     }
-    int rc = n ? api.wfa_extend(ctx, index, model, problems.data(), n, results.data(), nullptr, 0, nullptr, 0, written) : VGK_OK;        // scores only
+    int rc = n_wfa ? api.wfa_extend(ctx, index, model, to_wfa, n_wfa, results.data(), nullptr, 0, nullptr, 0, written) : VGK_OK;        // scores only
     if (rc != VGK_OK && rc != VGK_ETOOBIG) return rc;                         // (single declined problems are in results[].status)
     lap(0);
     // 2. the declined links as align_sequence_between requests
@@ -60,12 +71,18 @@ int run_chain_stage(const EngineApi& api, vgk_ctx* ctx, const vgk_haplo* index, 
     ChainConnector connector(aligner, graph, in.max_dp_cells);
     auto position = [&](uint32_t oriented, int64_t offset) { Position p; const handle_t h = graph.handle_of(oriented); p.node_id = graph.get_id(h); p.is_reverse = graph.get_is_reverse(h); p.offset = offset; return p; };
     for (uint32_t i = 0; i < n; ++i) {
-        const vgk_wfa_result& r = results[i];
-        if (r.status == VGK_OK && r.ok) { out.link_score[i] = r.score; out.link_source[i] = ChainStageOutput::WFA; continue; }
-        out.wfa_status[i] = r.status != VGK_OK ? r.status : VGK_ENOBAND;
-        ++out.n_declined;
         const bool connect = in.mode[i] == VGK_WFA_CONNECT;
-        if (connect && in.graph_distance && in.graph_distance[i] == 0 && problems[i].seq_len) {       // nothing lies between the anchors: the link is an insertion (:2996-3008)
+        const bool through_wfa = wfa_number(i) != NOT_WFA;
+        if (!through_wfa) {
+            if (in.route[i] == VGK_CHAIN_ROUTE_EMPTY) { out.link_source[i] = ChainStageOutput::EMPTY; continue; }
+            if (in.route[i] != VGK_CHAIN_ROUTE_DP) continue;                     // a soft-clipped tail: nothing aligned, score 0
+        } else {
+            const vgk_wfa_result& r = results[wfa_number(i)];
+            if (r.status == VGK_OK && r.ok) { out.link_score[i] = r.score; out.link_source[i] = ChainStageOutput::WFA; continue; }
+            out.wfa_status[i] = r.status != VGK_OK ? r.status : VGK_ENOBAND;
+            ++out.n_declined;
+        }
+        if (through_wfa && connect && in.graph_distance && in.graph_distance[i] == 0 && problems[i].seq_len) {       // nothing lies between the anchors: the link is an insertion (:2996-3008)
             const int32_t len = (int32_t)problems[i].seq_len;
             out.link_score[i] = -((int32_t)aligner.scorer->gap_open + (len - 1) * (int32_t)aligner.scorer->gap_extension);      // score_gap (src/alignment_scorer.cpp:24-26)
             out.link_source[i] = ChainStageOutput::UNLOCALIZED; continue;
@@ -135,11 +152,12 @@ int run_chain_stage(const EngineApi& api, vgk_ctx* ctx, const vgk_haplo* index, 
         bool broken = false;
         if ((first == last || in.mode[first] != VGK_WFA_PREFIX) && a < a_end) anchor(a++);
         for (i = first; i < last && !broken; ++i) {
-            const vgk_wfa_result& w = results[i];
+            const vgk_wfa_result none{};
+            const vgk_wfa_result& w = wfa_number(i) != NOT_WFA ? results[wfa_number(i)] : none;
             const uint32_t len = problems[i].seq_len;
             switch (out.link_source[i]) {
                 case ChainStageOutput::WFA: {
-                    vgk_chain_piece pc{}; pc.kind = VGK_PIECE_LINK; pc.link = i;
+                    vgk_chain_piece pc{}; pc.kind = VGK_PIECE_LINK; pc.link = wfa_number(i);
                     if (in.mode[i] == VGK_WFA_PREFIX) unlocalized(w.seq_offset);                                        // the tail's unaligned start is soft-clipped (:2632-2640)
                     pieces.push_back(pc);
                     if (in.mode[i] == VGK_WFA_SUFFIX && w.seq_offset + w.length < len) unlocalized(len - (w.seq_offset + w.length));       // (:3176-3181)
@@ -160,6 +178,7 @@ int run_chain_stage(const EngineApi& api, vgk_ctx* ctx, const vgk_haplo* index, 
                     pieces.push_back(pc);
                     break; }
                 case ChainStageOutput::UNLOCALIZED: unlocalized(len); break;
+                case ChainStageOutput::EMPTY: break;                                                                     // WFAAlignment::make_empty: nothing to append
                 default:                                                                                                // nothing aligned this link
                     if (in.mode[i] == VGK_WFA_CONNECT) broken = true;                                                    // the chain stops here (:3057, :3093)
                     else unlocalized(len);                                                                               // a tail left unaligned: soft clip (:2674, :3217)

@@ -23,6 +23,11 @@ struct ChainStageInput {
     const uint32_t* graph_distance;                                     // per link, nullable: the chain's distance between the two anchors (:2950; default: the link's length)
     const uint32_t *read_begin, *read_length;                           // per link, nullable: where the link starts in its read and that read's length (for longest_detectable_gap_in_range)
     const int64_t* anchor_score;                                        // per read, nullable: what the anchors themselves contribute
+    // per link, nullable: VGK_CHAIN_ROUTE_* as vgk_chain_links decided it (include/vgk_engine.h).  NULL: every link goes to WFA first, as before.  With
+    // routes: the WFA links go to vgk_wfa_extend as a compacted problem list (a LINK piece names the compacted number); DP links skip WFA and become
+    // align_sequence_between requests directly (:3044-3106); EMPTY links score 0 and make no piece (:2928-2945); SOFTCLIP tails score 0 and become an
+    // insertion without a position (:2667-2680, :3217)
+    const uint32_t* route = nullptr;
     size_t max_dp_cells = SIZE_MAX;
     size_t max_tail_gap = SIZE_MAX, max_middle_gap = SIZE_MAX;          // MinimizerMapper::max_tail_gap / max_middle_gap
     unsigned threads = 0;
@@ -39,7 +44,8 @@ struct ChainStageInput {
 };
 struct ChainStageOutput {
     enum Source : uint8_t { WFA = 0, BETWEEN = 1 /* align_sequence_between */, NONE = 2 /* nothing aligned: scores 0 */,
-                            UNLOCALIZED = 3 /* a connect WFA declined between anchors at graph distance 0: an insertion without a position, score_gap (:2996-3008) */ };
+                            UNLOCALIZED = 3 /* a connect WFA declined between anchors at graph distance 0: an insertion without a position, score_gap (:2996-3008) */,
+                            EMPTY = 4 /* (with routes) the anchors abut in read and graph: no piece, score 0 */ };
     std::vector<int32_t> link_score; std::vector<uint8_t> link_source;
     std::vector<int32_t> wfa_status;                                    // per link: vgk_wfa_result.status (declined links: VGK_ETOOBIG ...), ok folded in as VGK_ENOBAND when !ok
     std::vector<int64_t> chain_score;                                   // per read

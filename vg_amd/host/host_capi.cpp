@@ -791,15 +791,17 @@ int vgh_connector_run(vgh_connector* c, int threads, double* ms, char* json_out,
 extern "C" {
 // w: the WFA handle (haplotype graph + index + aligner) of vgh_wfa_create.  stats: declined, between, no graph, too big, failed, broken reads; ms[6].
 // anchors (anchor_off ... anchor_nodes, all or none; chain_stage.hpp): with them one alignment per read is composed (vgk_chain_stitch) and stays with
-// the handle until the next call: sizes = {mappings, edits}; vgh_chain_stage_view hands out the arrays (no copy).
+// the handle until the next call: sizes = {mappings, edits}; vgh_chain_stage_view hands out the arrays (no copy).  route (nullable): per link
+// VGK_CHAIN_ROUTE_*, as vgk_chain_links decided it (chain_stage.hpp); NULL: every link through WFA first.
 int vgh_chain_stage(vgh_wfa* w, const char* seqs, const uint64_t* seq_off, uint32_t n_links, const uint32_t* mode, const uint32_t* from_node, const uint32_t* from_offset,
                     const uint32_t* to_node, const uint32_t* to_offset, const uint32_t* read_of, uint32_t n_reads, const uint32_t* graph_distance,
                     const uint32_t* read_begin, const uint32_t* read_length, const int64_t* anchor_score, int threads, int dp_for_tails,
                     int32_t* link_score, uint8_t* link_source, int32_t* wfa_status, int64_t* chain_score, uint64_t stats[6], double ms[6],
                     const uint64_t* anchor_off, const uint32_t* anchor_length, const uint32_t* anchor_node_offset, const uint64_t* anchor_path_off, const uint32_t* anchor_nodes,
-                    uint64_t sizes[2]) {
+                    uint64_t sizes[2], const uint32_t* route) {
     try {
         ChainStageInput in{};
+        in.route = route;
         in.seqs = seqs; in.seq_off = seq_off; in.n_links = n_links; in.mode = mode; in.from_node = from_node; in.from_offset = from_offset;
         in.to_node = to_node; in.to_offset = to_offset; in.read_of = read_of; in.n_reads = n_reads; in.graph_distance = graph_distance;
         in.read_begin = read_begin; in.read_length = read_length; in.anchor_score = anchor_score; in.threads = (unsigned)std::max(threads, 0);
@@ -1654,6 +1656,95 @@ int vgh_funnel_winners(const vgk_funnel_policy* policy, uint32_t n, const char* 
             n_reported[r] = (uint32_t)w.n_reported; unmapped[r] = w.unmapped ? 1 : 0;
         });
         return funnel_lay_out(n, of, score_off, score_cap, written, [&](uint64_t at, const std::pair<int32_t, vgk_funnel_pick>& x) { scores[at] = x.first; reported[at] = x.second; });
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+}  // extern "C"
+
+// ---- a chain's links (chain_links.hpp): the checker and CPU baseline of vgk_chain_links -----------------------------------------------------------------
+#include "chain_links.hpp"
+extern "C" {
+// vgk_chain_links' arguments less the context, chains dealt over `threads` host threads; the same codes
+int vgh_chain_links(const vgk_chain_links_scheme* scheme, uint32_t n_reads, const char* reads, const uint64_t* read_off, uint32_t n_sets, const uint64_t* anchor_off,
+                    const vgk_chain_anchor* anchors, const vgk_chain_site* sites, const uint32_t* items, size_t n_items, const uint64_t* dist_off, const vgk_chain_candidate* dist,
+                    uint32_t n_chains, const vgk_chain_problem* chains, vgk_chain_links_result* results, vgk_chain_link* links, size_t link_cap, uint32_t* kept, size_t kept_cap,
+                    char* seqs, uint64_t* seq_off, size_t seq_cap, size_t* written, int threads) {
+    try {
+        if (written) written[0] = written[1] = written[2] = 0;
+        if (!scheme) return VGK_EINVAL;
+        if (!n_chains) return VGK_OK;
+        // the call: offsets ascend from 0, every chain names a read and a set of the batch
+        if ((n_reads && read_off[0] != 0) || (n_sets && (anchor_off[0] != 0 || dist_off[0] != 0))) return VGK_EINVAL;
+        for (uint32_t r = 0; r < n_reads; ++r) if (read_off[r + 1] < read_off[r]) return VGK_EINVAL;
+        for (uint32_t s = 0; s < n_sets; ++s) if (anchor_off[s + 1] < anchor_off[s] || dist_off[s + 1] < dist_off[s]) return VGK_EINVAL;
+        for (uint32_t c = 0; c < n_chains; ++c) if (chains[c].read >= n_reads || chains[c].anchor_set >= n_sets) return VGK_EINVAL;
+        ChainLinksScheme S;
+        S.max_chain_connection = scheme->max_chain_connection; S.max_tail_length = scheme->max_tail_length; S.max_middle_dp_length = scheme->max_middle_dp_length;
+        S.max_tail_dp_length = scheme->max_tail_dp_length; S.max_dp_cells = scheme->max_dp_cells; S.max_skipped_bases = scheme->max_skipped_bases;
+        S.min_indel_avoid_bases = scheme->min_indel_avoid_bases; S.match = scheme->match; S.full_length_bonus = scheme->full_length_bonus;
+        auto key = [](const vgk_chain_candidate& e) { return (uint64_t)e.from << 32 | e.to; };
+        // a set's distances: both anchors in the set, strictly ascending
+        std::vector<uint8_t> set_ok(n_sets, 1);
+        over_reads(n_sets, threads, [&](uint32_t s) {
+            const uint64_t A = anchor_off[s + 1] - anchor_off[s];
+            for (uint64_t d = dist_off[s]; d < dist_off[s + 1]; ++d)
+                if (dist[d].from >= A || dist[d].to >= A || (d > dist_off[s] && key(dist[d - 1]) >= key(dist[d]))) set_ok[s] = 0;
+        });
+        std::vector<ChainLinks> out(n_chains);
+        over_reads(n_chains, threads, [&](uint32_t c) {
+            const vgk_chain_problem& ch = chains[c];
+            out[c].ok = false;
+            if (!ch.n_items || (uint64_t)ch.item_begin + ch.n_items > n_items || !set_ok[ch.anchor_set]) return;
+            const uint64_t a0 = anchor_off[ch.anchor_set], A = anchor_off[ch.anchor_set + 1] - a0;
+            std::vector<size_t> chain(ch.n_items);
+            for (uint32_t k = 0; k < ch.n_items; ++k) {
+                const uint32_t a = items[ch.item_begin + k];
+                if (a >= A || sites[a0 + a].end_offset == 0) return;
+                if (k && anchors[a0 + a].read_start < anchors[a0 + chain[k - 1]].read_start) return;
+                chain[k] = a;
+            }
+            // the anchors the chain names (the rest of the set is not looked at)
+            std::vector<LinkAnchor> to_chain(A);
+            for (size_t a : chain) {
+                LinkAnchor& x = to_chain[a]; const vgk_chain_site& st = sites[a0 + a];
+                x.start = anchors[a0 + a].read_start; x.size = anchors[a0 + a].length; x.start_pos = GraphPos{st.start_node, st.start_offset}; x.end_pos = GraphPos{st.end_node, st.end_offset};
+                x.skippable = (st.flags & VGK_CHAIN_SITE_SKIPPABLE) != 0;
+            }
+            const vgk_chain_candidate* lo = dist + dist_off[ch.anchor_set]; const vgk_chain_candidate* hi = dist + dist_off[ch.anchor_set + 1];
+            auto get_graph_distance = [&](size_t a, size_t b) -> size_t {
+                const vgk_chain_candidate want{(uint32_t)a, (uint32_t)b, 0};
+                const vgk_chain_candidate* e = std::lower_bound(lo, hi, want, [&](const vgk_chain_candidate& x, const vgk_chain_candidate& y) { return key(x) < key(y); });
+                if (e == hi || key(*e) != key(want) || e->graph_distance == 0xffffffffu) return std::numeric_limits<size_t>::max();
+                return e->graph_distance;
+            };
+            out[c] = chain_links(S, (size_t)(read_off[ch.read + 1] - read_off[ch.read]), to_chain, chain, get_graph_distance);
+        });
+        uint64_t n_links = 0, n_kept = 0, n_seq = 0;
+        for (uint32_t c = 0; c < n_chains; ++c) if (out[c].ok) { n_links += out[c].links.size(); n_kept += out[c].kept.size(); for (const ChainLink& l : out[c].links) n_seq += l.length; }
+        if (written) { written[0] = (size_t)n_links; written[1] = (size_t)n_kept; written[2] = (size_t)n_seq; }
+        if (n_links > link_cap || n_kept > kept_cap || (seqs && n_seq > seq_cap)) return VGK_EOPS;
+        uint64_t at_link = 0, at_kept = 0, at_seq = 0;
+        for (uint32_t c = 0; c < n_chains; ++c) {
+            vgk_chain_links_result R{};
+            if (!out[c].ok) { R.status = VGK_EINVAL; results[c] = R; continue; }
+            const ChainLinks& o = out[c];
+            R.status = VGK_OK; R.flags = o.cut ? VGK_CHAIN_LINKS_CUT : 0; R.link_begin = (uint32_t)at_link; R.n_links = (uint32_t)o.links.size(); R.kept_begin = (uint32_t)at_kept;
+            R.n_kept = (uint32_t)o.kept.size(); R.left_tail_length = (uint32_t)o.left_tail_length; R.longest_attempted_connection = (uint32_t)o.longest_attempted_connection;
+            R.anchor_score = o.anchor_score; R.seq_begin = at_seq;
+            results[c] = R;
+            const char* read = reads ? reads + read_off[chains[c].read] : nullptr;
+            for (const ChainLink& l : o.links) {
+                vgk_chain_link L;
+                L.mode = l.mode; L.route = l.route; L.from_node = l.from.node; L.from_offset = l.from.offset; L.to_node = l.to.node; L.to_offset = l.to.offset;
+                L.read_begin = (uint32_t)l.read_begin; L.length = (uint32_t)l.length;
+                L.graph_distance = l.graph_distance > 0xffffffffull ? 0xffffffffu : (uint32_t)l.graph_distance; L.chain = c;
+                links[at_link] = L;
+                if (seqs) { seq_off[at_link] = at_seq; std::memcpy(seqs + at_seq, read + l.read_begin, l.length); }
+                ++at_link; at_seq += l.length;
+            }
+            for (size_t a : o.kept) kept[at_kept++] = (uint32_t)a;
+        }
+        if (seqs) seq_off[at_link] = at_seq;
+        return VGK_OK;
     } catch (std::exception& e) { g_last_error = e.what(); return -1; }
 }
 }  // extern "C"

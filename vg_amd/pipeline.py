@@ -644,11 +644,57 @@ def extension_anchors(eng, index, problems, match=1, mismatch=4, max_mismatches=
     return out
 
 
+def chain_links(eng, scheme, reads, read_off, anchor_off, anchors, sites, items, dist_off, dist, chains, threads=0):
+    """vgk_chain_links for a batch of chosen chains (include/vgk_engine.h): the link table and the kept anchors find_chain_alignment's walk decides on.
+    eng None: the host shim (vgh_chain_links, chains dealt over `threads` host threads) -> capi.chain_links_call's dict"""
+    if eng is None:
+        rc, out = capi.chain_links_call(_host_lib().vgh_chain_links, (), scheme, reads, read_off, anchor_off, anchors, sites, items, dist_off, dist, chains,
+                                        tail=(ctypes.c_int(threads),))
+        if rc:
+            raise RuntimeError("vgh_chain_links: %d" % rc)
+        return out
+    return eng.chain_links(scheme, reads, read_off, anchor_off, anchors, sites, items, dist_off, dist, chains)[1]
+
+
+def chains_to_stage_input(graph_of, out, chains, read_off, anchor_off, anchor_length, anchor_node_offset, anchor_path_off, anchor_nodes, route=True):
+    """what ChainStage reads, from chain_links' answer `out`: one stage read per chain — its links as the table (mode, end points, bases, graph distance,
+    where each starts in its read, that read's length), its kept anchors' anchor_length, anchor_node_offset, anchor_path_off and anchor_nodes gathered by
+    kept[] (anchor_* are the sets' own arrays, set s at anchor_off[s]), anchor_score as anchor_bases, and `route` (False: left out, every link through
+    WFA first).  graph_of: the object that holds the graph and the haplotype threads (a LongReadWorkload).  Every chain must have answered VGK_OK."""
+    import types
+    res, links = out["results"], out["links"]
+    ch = np.ascontiguousarray(chains, dtype=capi.CHAIN_PROBLEM_DT)
+    if (res["status"] != capi.VGK_OK).any():
+        raise ValueError("chains_to_stage_input: a chain was refused")
+    lens = np.diff(np.asarray(read_off).astype(np.int64))
+    kept_chain = np.repeat(np.arange(len(ch)), res["n_kept"].astype(np.int64))
+    g = np.asarray(anchor_off).astype(np.int64)[ch["anchor_set"][kept_chain]] + out["kept"].astype(np.int64)
+    po = np.asarray(anchor_path_off).astype(np.int64)
+    n_path = po[g + 1] - po[g]
+    new_po = np.concatenate([[0], np.cumsum(n_path)])
+    nodes = np.asarray(anchor_nodes)[np.repeat(po[g], n_path) + np.arange(int(new_po[-1])) - np.repeat(new_po[:-1], n_path)] if len(g) else np.zeros(0, dtype=np.uint32)
+    w = types.SimpleNamespace()
+    for k in ("graph", "nodes", "preds", "threads"):
+        if k in graph_of.__dict__ or k == "threads":
+            setattr(w, k, getattr(graph_of, k))
+    w.ws = types.SimpleNamespace(array=links, seqs=np.ascontiguousarray(out["seqs"]) if len(out["seqs"]) else np.zeros(1, np.uint8), seq_off=out["seq_off"])
+    w.n = len(links); w.n_reads = len(ch); w.read_of = links["chain"]; w.span = links["graph_distance"]
+    w.link_begin = links["read_begin"]; w.link_read_length = lens[ch["read"][links["chain"]]]
+    w.anchor_bases = res["anchor_score"]
+    w.anchor_off = np.concatenate([[0], np.cumsum(res["n_kept"].astype(np.int64))]).astype(np.uint64)
+    w.anchor_length = np.ascontiguousarray(np.asarray(anchor_length)[g], dtype=np.uint32); w.anchor_node_offset = np.ascontiguousarray(np.asarray(anchor_node_offset)[g], dtype=np.uint32)
+    w.anchor_path_off = new_po.astype(np.uint64); w.anchor_nodes = np.ascontiguousarray(nodes, dtype=np.uint32)
+    w.route = np.ascontiguousarray(links["route"]) if route else None
+    return w
+
+
 class ChainStage:
     """MinimizerMapper's chain alignment for a batch of reads, in C++ behind one call (vgh_chain_stage): every link through WFAExtender;
     what it declines through align_sequence_between_consistently — the local graph between / beyond the anchors cut out of the haplotype
     graph (extract_connecting_graph / extract_extending_graph), strands split, dagified, tips trimmed, then BandedGlobalAligner or pinned
-    X-drop — all inside the call.  Owns a host-shim aligner (its own engine context), the haplotype graph and the WFA extender."""
+    X-drop — all inside the call.  Owns a host-shim aligner (its own engine context), the haplotype graph and the WFA extender.
+    wl: a LongReadWorkload, or any plain object with the attributes read here (chains_to_stage_input makes one from vgk_chain_links' answer); its optional
+    `route` (per link CHAIN_ROUTE_*) sends only the WFA links to WFA, the DP links straight to align_sequence_between, and aligns nothing for the rest."""
 
     def __init__(self, wl, lib=None, scores=(1, 4, 6, 1, 5), device=0):
         h = _host_lib()
@@ -666,7 +712,7 @@ class ChainStage:
         h.vgh_wfa_last_kernel_ms.restype = ctypes.c_double; h.vgh_wfa_last_kernel_ms.argtypes = [ctypes.c_void_p]
         h.vgh_wfa_last_wave.restype = ctypes.c_double; h.vgh_wfa_last_wave.argtypes = [ctypes.c_void_p, ctypes.c_int]
         h.vgh_chain_stage.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6 + [ctypes.c_uint32] + [ctypes.c_void_p] * 4 + \
-                                     [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_void_p] * 6
+                                     [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_void_p] * 6 + [ctypes.c_void_p]
         h.vgh_chain_stage_view.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_void_p)] * 4 + [ctypes.POINTER(ctypes.c_double)]
         self.h = h
         self.aligner = h.vgh_aligner_create(lib.encode() if lib else None, device, *scores)
@@ -707,6 +753,7 @@ class ChainStage:
         h.vgh_wfa_host_register.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int]
         self.registered = h.vgh_wfa_host_register(self.wfa, self.seqs.ctypes.data, self.seqs.nbytes, 1) == 0 and self.seqs.nbytes > 0      # (the links' sequences go up by DMA from here)
         self.anchors = [np.ascontiguousarray(getattr(wl, k)) for k in ("anchor_off", "anchor_length", "anchor_node_offset", "anchor_path_off", "anchor_nodes")] if hasattr(wl, "anchor_off") else None
+        self.route = np.ascontiguousarray(wl.route, dtype=np.uint32) if getattr(wl, "route", None) is not None else None
 
     def set_point_budgets(self, connect, tail):
         self.h.vgh_wfa_set_point_budgets(self.wfa, connect, tail)
@@ -722,7 +769,7 @@ class ChainStage:
         rc = self.h.vgh_chain_stage(self.wfa, self.seqs.ctypes.data, self.seq_off.ctypes.data, self.n, *[f.ctypes.data for f in self.fields], self.read_of.ctypes.data,
                                     self.n_reads, self.graph_distance.ctypes.data, self.read_begin.ctypes.data, self.read_length.ctypes.data, self.anchor_score.ctypes.data,
                                     threads, int(dp_for_tails), link_score.ctypes.data, source.ctypes.data, status.ctypes.data, chain.ctypes.data, stats.ctypes.data, ms.ctypes.data,
-                                    *anchors, sizes.ctypes.data)
+                                    *anchors, sizes.ctypes.data, None if self.route is None else self.route.ctypes.data)
         if rc:
             raise RuntimeError("vgh_chain_stage: " + (self.h.vgh_last_error() or b"?").decode())
         if timing is not None:

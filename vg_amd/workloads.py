@@ -911,6 +911,48 @@ class LongReadWorkload:
             return self.__dict__["preds"]
         raise AttributeError(name)
 
+    def whole_reads(self):
+        """the reads themselves, which the link table only holds in pieces: read r = its links and, between them, its anchors' bases along anchor_nodes
+        on the read's strand — what vgk_chain_links takes.  -> dict(reads uint8, read_off uint64, read_start per anchor (where it starts in its read),
+        sites capi.CHAIN_SITE_DT per anchor: graph_start = the anchor's first base, graph_end = past its last base within the node that holds it)"""
+        from . import capi
+        comp = _comp_table()
+        if self.__dict__.get("graph") is not None:
+            g = self.graph; col = g.col
+            node_seq = lambda v: g.seq[int(col[v]):int(col[v + 1])]
+        else:
+            node_seq = lambda v: np.frombuffer(self.nodes[v].encode(), dtype=np.uint8)
+        oriented = lambda o: node_seq(o >> 1) if not o & 1 else comp[node_seq(o >> 1)[::-1]]
+        mode = self.ws.array["mode"]; seqs = self.ws.seqs; seq_off = self.ws.seq_off
+        n_anchors = len(self.anchor_length)
+        sites = np.zeros(n_anchors, dtype=capi.CHAIN_SITE_DT); read_start = np.zeros(n_anchors, dtype=np.uint32)
+        parts, read_off, i = [], [0], 0
+        for r in range(self.n_reads):
+            at = 0; a = int(self.anchor_off[r]); a_end = int(self.anchor_off[r + 1])
+
+            def anchor(a, at):
+                path = [int(x) for x in self.anchor_nodes[int(self.anchor_path_off[a]):int(self.anchor_path_off[a + 1])]]
+                off, length = int(self.anchor_node_offset[a]), int(self.anchor_length[a])
+                bases = np.concatenate([oriented(o) for o in path])[off:off + length]
+                assert len(bases) == length
+                left = off + length                                    # bases from the first node's start to the anchor's end
+                for o in path:
+                    if left <= len(node_seq(o >> 1)):
+                        sites[a] = (path[0], off, o, left, 0); break
+                    left -= len(node_seq(o >> 1))
+                read_start[a] = at; parts.append(bases)
+                return at + length
+            if (i >= self.n or self.read_of[i] != r or mode[i] != capi.WFA_PREFIX) and a < a_end:
+                at = anchor(a, at); a += 1
+            while i < self.n and self.read_of[i] == r:
+                piece = seqs[int(seq_off[i]):int(seq_off[i + 1])]
+                parts.append(piece); at += len(piece)
+                if mode[i] != capi.WFA_SUFFIX and a < a_end:
+                    at = anchor(a, at); a += 1
+                i += 1
+            read_off.append(read_off[-1] + at)
+        return dict(reads=np.concatenate(parts).astype(np.uint8) if parts else np.zeros(0, dtype=np.uint8), read_off=np.array(read_off, dtype=np.uint64), read_start=read_start, sites=sites)
+
     def prepare_connects(self):
         """every connect's graph between its anchors (between()) laid out once in one flat BandedSet: `connects`, `connect_row[i]` = problem
         i's row in it (-1: not a connect).  What a caller holds after vg's extract_connecting_graph; chain_stage picks its fallback batch
