@@ -128,6 +128,17 @@ tests/emu/chain_links_san: tests/emu/chain_links_driver.cpp $(LIB_HDRS)
 	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -DCL_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 .PHONY: chainlinks chainlinks_san
 
+# test-only: the serial composition of the device rule for a long read's mappings — the checks, the statistics, multiplicities and sort scores, the pick
+# on one lane (pick_mappings_device.hpp: pick_check_one, pick_stat_one, pick_alignment_one, pick_read_one) behind one C call, and the same as a program of
+# its own under the host sanitizers
+pickmappings: tests/emu/libvgamd_pickmappings.so
+tests/emu/libvgamd_pickmappings.so: tests/emu/pick_mappings_driver.cpp $(LIB_HDRS)
+	$(CXX) -O2 -g -std=c++17 -fPIC -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -shared -o $@ $<
+pickmappings_san: tests/emu/pick_mappings_san
+tests/emu/pick_mappings_san: tests/emu/pick_mappings_driver.cpp $(LIB_HDRS)
+	$(CXX) -O1 -g -std=c++17 -Iinclude -Wall -Wno-unknown-pragmas -ffp-contract=off -DPICK_DRIVER_MAIN -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+.PHONY: pickmappings pickmappings_san
+
 # test-only: the serial form of the device rule for a pair's mapping qualities — pair scores, their order, the shared caps (pair_mapq_device.hpp:
 # pm_candidate_score, pm_pair_one; the mates' caps by read_mapq_device.hpp's mq_cap_one) behind one C call, and the same as a program of its own under
 # the host sanitizers

@@ -573,6 +573,79 @@ int vgk_chain_links(vgk_ctx* ctx, const vgk_chain_links_scheme* scheme, uint32_t
 /* Device time (ms) of the last vgk_chain_links call on this context: checks + walk | counts, prefix sums and write-out | sequences */
 int vgk_chain_links_last_ms(vgk_ctx* ctx, double ms[3]);
 
+/* ---- a long read's mappings chosen on the device: scores, order, uniqueness ------------------------------------------------------------------------
+ * The end of MinimizerMapper::do_alignment_on_chains (the multiplicity fix-up, src/minimizer_mapper_from_chains.cpp:2241-2262, with
+ * chain_ranges_are_equivalent :100-191) followed by pick_mappings_from_alignments (:2265-2493): the step between the chain stage, which answers with
+ * one composed alignment per chain, and vgk_read_mapq, which wants a read's scores in their final order, a multiplicity per score and an unmapped
+ * byte.  No distance index and no zip code is read: the four numbers of a chain's range are GIVEN.  The rule is stated serially in
+ * vg_amd/csrc/pick_mappings_device.hpp, which the kernels call; the host shim (vg_amd/host/pick_mappings.cpp: vgh_pick_mappings) states it in the
+ * reference's shape and is the checker.  No reference unit test names these loops [PARITY-UNPINNED]: the rule is held to a second statement in
+ * tests/test_pick_mappings.py.
+ *
+ * In.  Reads as `reads` / read_off[n_reads + 1] (read for the generator's seed only; nullable when rng_state is).  rng_state: one uint32 per read
+ * in vgk_funnel_*'s convention (0: not made yet), updated in place; NULL: nothing is shuffled.  Read r's chains are chains[chain_off[r] ..
+ * chain_off[r + 1]): score_estimate (chain_score_estimates), multiplicity (multiplicity_by_chain) and its range {component =
+ * get_distance_index_address(0), flags (VGK_CHAIN_RANGE_ROOT_SNARL: get_code_type(0) == ROOT_SNARL), child_start / child_end = get_rank_in_snarl(1)
+ * of the chain's first / last seed, offset_start / offset_end = get_seed_offset of the same two seeds}.  Its alignments are alns[aln_off[r] ..
+ * aln_off[r + 1]) in the order do_alignment_on_chains made them: source (a chain of the read, numbered within the read), item_count (the
+ * better_or_equal_count its chain's walk passed in, :2142), score (final: no softclip_penalty is applied here) and a vgk_chain_result naming its
+ * mappings mappings[mapping_begin .. + n_mappings) in vgk_chain_stitch's layout — per mapping {oriented node or VGK_WFA_NO_NODE, offset, edit_begin,
+ * n_edits}, its runs edits[edit_begin .. + n_edits) as length << 2 | VGK_WFA_*.  Only mapping_begin and n_mappings of the result are read.  Two
+ * results may name the same mappings.
+ *
+ * The rule.  Equivalent ranges (:100-191): different components: no; when chain 1 is in a root snarl and child_start1 != child_start2 or
+ * child_start1 != child_end1 or child_start2 != child_end2: no; each chain's two offsets swapped into order; disjoint: no; one contains the other:
+ * yes; otherwise overlap > min(len1, len2) / 2 (integer division).  count[i] = item_count[i] less one for every j != i with estimate[source[i]] >=
+ * estimate[source[j]] and equivalent ranges; multiplicity[i] = chain multiplicity + (count >= A ? (double)count - (double)A : 0.0), A = the read's
+ * alignments.  THE WRAP: count is the reference's size_t and wraps below 0 here as there — a best chain with item_count 1 and two equivalent lower
+ * chains aligned has count 2^64 - 1 and multiplicity + 2^64 - A.  identity (src/path.cpp:2316-2335) = matched bases / to_length, the length less an
+ * insertion that is the path's very first or very last edit (an edit that is both: once), 0.0 when that length is 0.  A mapping's from_length = its
+ * match, mismatch and deletion runs; a mapping without a node has none and is never entered into the used set.  The walk is
+ * process_until_threshold_a: descending by (double)score + identity — or (double)estimate[source] under VGK_PICK_SORT_BY_CHAIN_SCORE — ties at the top
+ * shuffled by the read's generator, threshold 0, min 1, max max_multimaps.  Processed (:2334-2404): score <= 0 fails and does not count; fraction
+ * unique = (double)(total - used) / total over its mappings' from_lengths (1.0 when total is 0), used = on oriented nodes of the alignments accepted
+ * before it; fraction < min_unique_node_fraction fails and does not count; otherwise its nodes are marked, score and multiplicity are appended and
+ * it is a mapping.  Beyond the cut (:2405-2466): the same two filters without marking; survivors append score and multiplicity only.  No mapping:
+ * one entry of score 0 and multiplicity 0, unmapped = 1 (:2480-2486).
+ *
+ * Out.  Per read {status, first, n_scores, n_mappings, unmapped}: picked[first .. + n_scores) (the alignment's number within the read; UINT32_MAX
+ * for the unmapped entry), scores[] and multiplicity[] beside it, in walk order; the first n_mappings of them are the mappings; first = aln_off[r]
+ * + r.  Per alignment {identity, fraction_unique, fate}: fraction_unique is VGK_PICK_NOT_EVALUATED's bits (a quiet NaN) where score <= 0 kept it
+ * from being computed; fate one of VGK_PICK_MAPPING, _BEYOND_CUT, _FAIL_SCORE, _FAIL_UNIQUE.
+ * Room: `cap` entries of picked / scores / multiplicity, aln_off[n_reads] + n_reads needed; VGK_EOPS when short, *written = what is needed and
+ * nothing else is written.  VGK_ETOOBIG, before anything is allocated, when reads, chains, alignments + reads, mappings, edits or the sum of the
+ * alignments' mapping counts (in 64 bits) exceed 2^32 - 16.
+ * Per read VGK_EINVAL, every other field 0 and its alignments' verdicts 0, the rest of the call answers: a source outside the read's chains; a
+ * result whose mappings, or a mapping of it whose runs, lie outside the arrays; a chain multiplicity that is not finite.  For the call VGK_EINVAL:
+ * offsets that do not ascend from 0, unknown flags, max_multimaps 0, a min_unique_node_fraction that is NaN, rng_state without reads.  No reads:
+ * VGK_OK.
+ * Not here: zip-code decoding of the ranges, softclip_penalty, the chain walk that makes item_count, set_refpos, annotations; the resident form
+ * (alignments taken where vgk_chain_stitch left them in HBM) is not built. */
+enum { VGK_PICK_SORT_BY_CHAIN_SCORE = 1 };   /* vgk_pick_scheme.flags: sort_by_chain_score */
+enum { VGK_CHAIN_RANGE_ROOT_SNARL = 1 };     /* vgk_chain_range.flags */
+enum { VGK_PICK_MAPPING = 1, VGK_PICK_BEYOND_CUT = 2, VGK_PICK_FAIL_SCORE = 3, VGK_PICK_FAIL_UNIQUE = 4 };   /* vgk_pick_verdict.fate */
+#define VGK_PICK_NOT_EVALUATED 0x7ff8000000000000ull   /* the bits of fraction_unique where it was never evaluated */
+typedef struct vgk_pick_scheme { double min_unique_node_fraction; /* [0.0] */ uint32_t max_multimaps; /* [1] */ uint32_t flags; } vgk_pick_scheme;   /* 16 B */
+typedef struct vgk_chain_range { uint64_t component; uint32_t flags, child_start, child_end, reserved; uint64_t offset_start, offset_end; } vgk_chain_range;   /* 40 B */
+typedef struct vgk_pick_chain { int32_t score_estimate; uint32_t reserved; double multiplicity; vgk_chain_range range; } vgk_pick_chain;            /* 56 B */
+typedef struct vgk_pick_alignment { uint32_t source; int32_t score; uint64_t item_count; vgk_chain_result result; } vgk_pick_alignment;             /* 48 B */
+typedef struct vgk_pick_result { int32_t status; uint32_t first, n_scores, n_mappings, unmapped, reserved; } vgk_pick_result;                       /* 24 B */
+typedef struct vgk_pick_verdict { double identity, fraction_unique; uint32_t fate, reserved; } vgk_pick_verdict;                                    /* 24 B */
+int vgk_pick_mappings(vgk_ctx* ctx, const vgk_pick_scheme* scheme, uint32_t n_reads, const char* reads /* nullable */, const uint64_t* read_off,
+                      uint32_t* rng_state /* nullable */, const uint64_t* chain_off, const vgk_pick_chain* chains, const uint64_t* aln_off,
+                      const vgk_pick_alignment* alns, const vgk_chain_mapping* mappings, size_t n_mappings, const uint32_t* edits, size_t n_edits,
+                      vgk_pick_result* results /* [n_reads] */, vgk_pick_verdict* verdicts /* [aln_off[n_reads]] */, uint32_t* picked, int32_t* scores,
+                      double* multiplicity, size_t cap, size_t* written);
+/* out[0] = distinct oriented nodes a read's accepted alignments may hold (the sum of the mapping counts of its max_multimaps largest alignments)
+ * with the used set in LDS, out[1] = the slots of that table (open addressing, linear probing from (node * 2654435761 mod 2^32) >> (32 - log2
+ * slots)), out[2] = alignments of a read whose walk order lies in LDS, out[3] = lanes per read in the pick.  Reads beyond out[0] or out[2] run in a
+ * second launch over a slab in HBM */
+int vgk_pick_mappings_limits(uint32_t out[4]);
+/* Device time (ms) of the last vgk_pick_mappings call on this context: checks | statistics | multiplicities and sort scores | the pick */
+int vgk_pick_mappings_last_ms(vgk_ctx* ctx, double ms[4]);
+/* Reads of the last vgk_pick_mappings call by where the pick ran: in LDS | over the slab | refused by the checks */
+int vgk_pick_mappings_last_launches(vgk_ctx* ctx, uint64_t reads[3]);
+
 /* ---- windows of the resident graph, of any read length: the wide route on the device ------------------------------------------------------
  * vgk_gssw_pack_windows (vgk.h) takes what the packed kernels take: at most 1024 DP rows, scores inside 11 bits; a longer window fails the whole
  * pack with VGK_ETOOLONG.  This one-call entry takes windows of any read length and scoring and answers every problem in its own status, as

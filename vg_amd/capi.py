@@ -500,6 +500,66 @@ assert BANDED_DT.itemsize == 80
 assert GRAPH_DT.itemsize == 40 and PROBLEM_DT.itemsize == 80 and RESULT_DT.itemsize == 32 and OP_DT.itemsize == 8
 
 
+# vgk_pick_mappings (include/vgk_engine.h): a long read's mappings chosen from its chains' alignments — multiplicities, order, uniqueness
+CHAIN_RANGE_DT = np.dtype([("component", "<u8"), ("flags", "<u4"), ("child_start", "<u4"), ("child_end", "<u4"), ("reserved", "<u4"), ("offset_start", "<u8"), ("offset_end", "<u8")])
+PICK_CHAIN_DT = np.dtype([("score_estimate", "<i4"), ("reserved", "<u4"), ("multiplicity", "<f8"), ("range", CHAIN_RANGE_DT)])
+PICK_ALIGNMENT_DT = np.dtype([("source", "<u4"), ("score", "<i4"), ("item_count", "<u8"), ("result", CHAIN_RESULT_DT)])
+PICK_RESULT_DT = np.dtype([("status", "<i4"), ("first", "<u4"), ("n_scores", "<u4"), ("n_mappings", "<u4"), ("unmapped", "<u4"), ("reserved", "<u4")])
+PICK_VERDICT_DT = np.dtype([("identity", "<f8"), ("fraction_unique", "<f8"), ("fate", "<u4"), ("reserved", "<u4")])
+assert CHAIN_RANGE_DT.itemsize == 40 and PICK_CHAIN_DT.itemsize == 56 and PICK_ALIGNMENT_DT.itemsize == 48 and PICK_RESULT_DT.itemsize == 24 and PICK_VERDICT_DT.itemsize == 24
+PICK_SORT_BY_CHAIN_SCORE = 1
+CHAIN_RANGE_ROOT_SNARL = 1
+PICK_MAPPING, PICK_BEYOND_CUT, PICK_FAIL_SCORE, PICK_FAIL_UNIQUE = 1, 2, 3, 4
+PICK_NOT_EVALUATED = 0x7ff8000000000000         # the bits of fraction_unique where it was never evaluated
+PICK_NONE = 0xffffffff                          # picked[]: the unmapped entry
+
+
+class PickScheme(ctypes.Structure):             # vgk_pick_scheme; the defaults are MinimizerMapper's
+    _fields_ = [("min_unique_node_fraction", ctypes.c_double), ("max_multimaps", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+    @classmethod
+    def defaults(cls, **changed):
+        p = cls(0.0, 1, 0)
+        for name, value in changed.items():
+            assert hasattr(p, name), name
+            setattr(p, name, value)
+        return p
+
+
+assert ctypes.sizeof(PickScheme) == 16
+
+
+def pick_mappings_call(fn, head, scheme, reads, read_off, chain_off, chains, aln_off, alns, mappings, edits, rng_state=None, tail=(), cap=None):
+    """one call with vgk_pick_mappings' arguments (the engine's, the host shim's vgh_pick_mappings, the serial driver's): head / tail = the ctypes values the
+    function takes before `scheme` / behind `written`.  rng_state: uint32 per read, updated in place (None: nothing is shuffled, the reads are not passed).
+    cap None: the room the header names (alignments + reads)
+    -> (rc, dict(results PICK_RESULT_DT, verdicts PICK_VERDICT_DT, picked, scores, multiplicity, written))"""
+    def ptr(a):
+        return a.ctypes.data if a is not None and len(a) else None
+    off = np.ascontiguousarray(read_off, dtype=np.uint64); coff = np.ascontiguousarray(chain_off, dtype=np.uint64); aoff = np.ascontiguousarray(aln_off, dtype=np.uint64)
+    rd = None if reads is None else np.ascontiguousarray(reads, dtype=np.uint8)
+    ch = np.ascontiguousarray(chains, dtype=PICK_CHAIN_DT); al = np.ascontiguousarray(alns, dtype=PICK_ALIGNMENT_DT)
+    mp = np.ascontiguousarray(mappings, dtype=CHAIN_MAPPING_DT); ed = np.ascontiguousarray(edits, dtype=np.uint32)
+    n = len(coff) - 1
+    assert len(aoff) == len(coff) == len(off) and (rng_state is None or (rng_state.dtype == np.uint32 and len(rng_state) == n and rng_state.flags.c_contiguous))
+    if cap is None:
+        cap = len(al) + n
+    cap = int(cap)
+    results = np.zeros(max(n, 1), dtype=PICK_RESULT_DT); verdicts = np.zeros(max(len(al), 1), dtype=PICK_VERDICT_DT)
+    picked = np.zeros(max(cap, 1), dtype=np.uint32); scores = np.zeros(max(cap, 1), dtype=np.int32); mult = np.zeros(max(cap, 1), dtype=np.float64)
+    written = ctypes.c_size_t(0)
+    fn.restype = ctypes.c_int
+    fn.argtypes = [type(t) for t in head] + [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 5 + \
+                  [ctypes.c_size_t, ctypes.c_void_p] + [type(t) for t in tail]
+    rc = fn(*head, ctypes.byref(scheme), n, ptr(rd) if rng_state is not None else None, off.ctypes.data, rng_state.ctypes.data if rng_state is not None and n else None,
+            coff.ctypes.data, ptr(ch), aoff.ctypes.data, ptr(al), ptr(mp), len(mp), ptr(ed), len(ed), results.ctypes.data, verdicts.ctypes.data, picked.ctypes.data, scores.ctypes.data,
+            mult.ctypes.data, cap, ctypes.byref(written), *tail)
+    w = int(written.value)
+    if rc != VGK_OK:
+        return rc, dict(results=results[:n], written=w)
+    return rc, dict(results=results[:n], verdicts=verdicts[:len(al)], picked=picked[:w], scores=scores[:w], multiplicity=mult[:w], written=w)
+
+
 class Scoring(ctypes.Structure):
     _fields_ = [("matrix", ctypes.c_int8 * 25), ("gap_open", ctypes.c_uint8), ("gap_extend", ctypes.c_uint8),
                 ("full_length_bonus", ctypes.c_int8), ("reserved", ctypes.c_uint8)]
@@ -1250,6 +1310,36 @@ class Engine:
         self.lib.vgk_chain_links_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._check(self.lib.vgk_chain_links_last_ms(self.h, ms), "vgk_chain_links_last_ms")
         return tuple(float(x) for x in ms)
+
+    def pick_mappings(self, scheme, reads, read_off, chain_off, chains, aln_off, alns, mappings, edits, rng_state=None, cap=None):
+        """vgk_pick_mappings (include/vgk_engine.h): per read the alignments picked as mappings or counted beyond the cut, their scores and multiplicities in walk
+        order, the unmapped flag; per alignment identity, unique fraction and fate.  scheme: a PickScheme; chains PICK_CHAIN_DT; alns PICK_ALIGNMENT_DT over
+        mappings CHAIN_MAPPING_DT and edit runs as vgk_chain_stitch leaves them -> (rc, dict), rc VGK_OK or VGK_EOPS"""
+        rc, out = pick_mappings_call(self.lib.vgk_pick_mappings, (self.h,), scheme, reads, read_off, chain_off, chains, aln_off, alns, mappings, edits, rng_state=rng_state, cap=cap)
+        if rc != VGK_EOPS:
+            self._check(rc, "vgk_pick_mappings")
+        return rc, out
+
+    def pick_mappings_last_ms(self):
+        """device time of the last pick_mappings call in ms: checks | statistics | multiplicities and sort scores | the pick"""
+        ms = (ctypes.c_double * 4)()
+        self.lib.vgk_pick_mappings_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_pick_mappings_last_ms(self.h, ms), "vgk_pick_mappings_last_ms")
+        return tuple(float(x) for x in ms)
+
+    def pick_mappings_last_launches(self):
+        """reads of the last pick_mappings call by where the pick ran: in LDS | over the slab | refused by the checks"""
+        reads = (ctypes.c_uint64 * 3)()
+        self.lib.vgk_pick_mappings_last_launches.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.vgk_pick_mappings_last_launches(self.h, reads), "vgk_pick_mappings_last_launches")
+        return tuple(int(x) for x in reads)
+
+    def pick_mappings_limits(self):
+        """(nodes in the LDS table, its slots, alignments whose order lies in LDS, lanes per read)"""
+        out = (ctypes.c_uint32 * 4)()
+        self.lib.vgk_pick_mappings_limits.argtypes = [ctypes.c_void_p]
+        self._check(self.lib.vgk_pick_mappings_limits(out), "vgk_pick_mappings_limits")
+        return tuple(int(x) for x in out)
 
     def pair_mapq(self, scheme, cand_off, candidates, counts, **rest):
         """vgk_pair_mapq (include/vgk_engine.h): per pair both mates' mapping qualities from its candidate pairings — pair scores, their order, the caps both

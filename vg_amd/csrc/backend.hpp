@@ -29,6 +29,7 @@
 #include "pair_mapq_device.hpp"
 #include "read_funnel_device.hpp"
 #include "chain_links_device.hpp"
+#include "pick_mappings_device.hpp"
 
 namespace vgk {
 
@@ -198,6 +199,11 @@ public:
     // per link slot (cl_write_one), the kept anchors' scores summed per chain into p.res[].anchor_score; CL_RUN_SEQS a wavefront per link of p.n_links: its
     // bases from the read into p.seqs.  Asynchronous on the main stream.  Optional
     virtual int   run_chain_links(const ClParams& p, int what) { (void)p; (void)what; return VGK_EUNSUPPORTED; }
+    // vgk_pick_mappings (pick_mappings_device.hpp), one stage per call: PICK_RUN_CHECK a lane per alignment and per chain (pick_check_one); PICK_RUN_STATS a
+    // lane per mapping slot (pick_stat_one), matched bases and to_length summed per alignment into p.sums; PICK_RUN_ALIGNMENTS a lane per alignment
+    // (pick_alignment_one); PICK_RUN_PICK a wavefront per read of p.ids[0 .. p.n) (pick_read_one), order and used set in LDS — or, with p.slab, `blocks`
+    // wavefronts striding over the reads, each over its own slab.  Asynchronous on the main stream.  Optional
+    virtual int   run_pick_mappings(const PickParams& p, int what, uint32_t blocks) { (void)p; (void)what; (void)blocks; return VGK_EUNSUPPORTED; }
     virtual int   run_tail(const TailParams& p, uint32_t threads) = 0;
     virtual int   run_tail_stage(const TStageParams& p, int what) = 0;     // one of the per-item stages of vgk_tail_stage (tail_device.hpp: TS_*)
     virtual int   run_rescue_requests(const RqParams& p, int what) = 0;    // one of the per-pair stages of vgk_rescue_requests (rescue_requests_device.hpp: RQ_*)

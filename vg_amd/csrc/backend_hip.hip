@@ -1450,6 +1450,63 @@ __global__ void __launch_bounds__(256) chain_links_seq_kernel(const ClParams P) 
         for (uint32_t k = lane; k < len; k += 64) dst[k] = src[k];
     }
 }
+// ---- a long read's mappings (pick_mappings_device.hpp: pick_alignment_one and pick_read_one are the rule and the checker).  The checks a lane per
+// alignment and per chain, the statistics a lane per mapping slot with the two sums of an alignment as segmented wavefront sums, multiplicities and sort
+// scores a lane per alignment; the pick a wavefront per read: all 64 lanes go through the one walk, share out an alignment's mappings for its fraction
+// and its marks, and keep the walk's order and the used-node table in LDS — or, for the reads beyond the limits, in the block's slab.
+__global__ void __launch_bounds__(256) pick_check_kernel(const PickParams P) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (uint64_t)P.n_alns + P.n_chains) pick_check_one(P, i);
+}
+// a wavefront's lanes of one alignment are neighbours: an inclusive scan that stops at the alignment's first lane leaves its share in its last lane of
+// the wavefront, which adds it: one atomic per wavefront, alignment and sum (integers: any order, one sum)
+__global__ void __launch_bounds__(256) pick_stats_kernel(const PickParams P) {
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const bool live = s < P.n_slots;
+    uint32_t aln = 0xffffffffu;
+    unsigned long long share[2] = {0, 0};
+    if (live) pick_stat_one(P, s, &aln, share);
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const unsigned long long up0 = __shfl_up(share[0], d, 64), up1 = __shfl_up(share[1], d, 64); const uint32_t up_aln = __shfl_up(aln, d, 64);
+        if (lane >= d && up_aln == aln) { share[0] += up0; share[1] += up1; }
+    }
+    const uint32_t down_aln = __shfl_down(aln, 1, 64);
+    if (live && (lane == 63 || down_aln != aln)) {
+        if (share[0]) atomicAdd(P.sums + 2 * (uint64_t)aln, share[0]);
+        if (share[1]) atomicAdd(P.sums + 2 * (uint64_t)aln + 1, share[1]);
+    }
+}
+__global__ void __launch_bounds__(256) pick_alignments_kernel(const PickParams P) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < P.n_alns) pick_alignment_one(P, i);
+}
+// the 64 lanes of a pick.  LDS: the table is the block's own, a barrier orders its compare-and-swaps before the plain loads
+struct PickWaveLds {
+    uint32_t lane, lanes;
+    __device__ unsigned long long sum(unsigned long long x) const { for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64); return x; }
+    __device__ void sync() const { __syncthreads(); }
+    __device__ uint32_t load(const uint32_t* p) const { return *p; }
+    __device__ void store(uint32_t* p, uint32_t v) const { *p = v; }
+    __device__ uint32_t cas(uint32_t* p, uint32_t expect, uint32_t v) const { return atomicCAS(p, expect, v); }
+};
+// the slab: the table lies in HBM, where compare-and-swap is done at L2; loads and stores of it go there too, past the CU's own cache
+struct PickWaveSlab {
+    uint32_t lane, lanes;
+    __device__ unsigned long long sum(unsigned long long x) const { for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64); return x; }
+    __device__ void sync() const { __threadfence(); __syncthreads(); }
+    __device__ uint32_t load(const uint32_t* p) const { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ void store(uint32_t* p, uint32_t v) const { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ uint32_t cas(uint32_t* p, uint32_t expect, uint32_t v) const { return atomicCAS(p, expect, v); }
+};
+__global__ void __launch_bounds__(64) pick_kernel(const PickParams P) {
+    __shared__ uint32_t order[FN_LDS_ITEMS];
+    __shared__ uint32_t table[PICK_LDS_SLOTS];
+    pick_read_one(P, P.ids[blockIdx.x], order, table, PICK_LDS_SLOTS, PickWaveLds{threadIdx.x, 64u});
+}
+__global__ void __launch_bounds__(64) pick_slab_kernel(const PickParams P) {
+    uint32_t* order = (uint32_t*)(P.slab + (uint64_t)blockIdx.x * P.slab_stride);
+    for (uint32_t i = blockIdx.x; i < P.n; i += gridDim.x) { pick_read_one(P, P.ids[i], order, order + P.slab_items, P.slab_slots, PickWaveSlab{threadIdx.x, 64u}); __syncthreads(); }
+}
 __global__ void __launch_bounds__(64) chain_stitch_kernel(const CsParams P, const int what) {
     cs_one(P, what, blockIdx.x * 64 + threadIdx.x);
 }
@@ -2375,6 +2432,21 @@ public:
         else if (what == CL_RUN_COUNT) hipLaunchKernelGGL(chain_links_count_kernel, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, stream, p);
         else if (what == CL_RUN_WRITE) hipLaunchKernelGGL(chain_links_write_kernel, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, stream, p);
         else if (what == CL_RUN_SEQS) hipLaunchKernelGGL(chain_links_seq_kernel, dim3((uint32_t)((lanes + 3) / 4)), dim3(256), 0, stream, p);
+        else return VGK_EINVAL;
+        return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
+    }
+    int run_pick_mappings(const PickParams& p, int what, uint32_t blocks) override {
+        hipSetDevice(dev);
+        if (what == PICK_RUN_PICK) {
+            if (!blocks) return VGK_OK;
+            return launch_lds_or_slab(pick_kernel, pick_slab_kernel, p.slab, blocks, 0, p);
+        }
+        const uint64_t lanes = what == PICK_RUN_CHECK ? (uint64_t)p.n_alns + p.n_chains : what == PICK_RUN_STATS ? p.n_slots : p.n_alns;
+        if (!lanes) return VGK_OK;
+        const dim3 grid((uint32_t)((lanes + 255) / 256));
+        if (what == PICK_RUN_CHECK) hipLaunchKernelGGL(pick_check_kernel, grid, dim3(256), 0, stream, p);
+        else if (what == PICK_RUN_STATS) hipLaunchKernelGGL(pick_stats_kernel, grid, dim3(256), 0, stream, p);
+        else if (what == PICK_RUN_ALIGNMENTS) hipLaunchKernelGGL(pick_alignments_kernel, grid, dim3(256), 0, stream, p);
         else return VGK_EINVAL;
         return hipGetLastError() == hipSuccess ? VGK_OK : VGK_ENODEV;
     }

@@ -148,6 +148,8 @@ struct vgk_ctx {
     double funnel_ms[3] = {0, 0, 0};   // last vgk_funnel_clusters | vgk_funnel_extension_sets | vgk_funnel_winners
     uint64_t funnel_reads[3] = {0, 0, 0};   // reads of the last vgk_funnel_* call: everything in LDS | something over the slab | refused by the checks
     double chain_links_ms[3] = {0, 0, 0};   // last vgk_chain_links: checks + walk | counts, prefix sums and write-out | sequences
+    double pick_mappings_ms[4] = {0, 0, 0, 0};   // last vgk_pick_mappings: checks | statistics | multiplicities and sort scores | the pick
+    uint64_t pick_mappings_reads[3] = {0, 0, 0};   // reads of the last vgk_pick_mappings: picked in LDS | over the slab | refused by the checks
     double pair_mapq_ms[2] = {0, 0};   // last vgk_pair_mapq: the mates' sweep | the score and pair kernels
     uint32_t pair_mapq_launches[2] = {0, 0};   // kernels the last vgk_pair_mapq launched: the mates' sweep | scores and pairs
     uint64_t pair_mapq_pairs[3] = {0, 0, 0};   // pairs of the last vgk_pair_mapq: in LDS | over the slab | refused by the checks

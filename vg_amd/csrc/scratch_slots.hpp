@@ -83,6 +83,11 @@ enum Slot : int {
     CHAINLINKS_READS, CHAINLINKS_READ_OFF, CHAINLINKS_ANCHOR_OFF, CHAINLINKS_ANCHORS, CHAINLINKS_SITES, CHAINLINKS_ITEMS, CHAINLINKS_DIST_OFF, CHAINLINKS_DIST,
     CHAINLINKS_CHAINS, CHAINLINKS_SLOT_OFF, CHAINLINKS_BYTES, CHAINLINKS_COUNT, CHAINLINKS_FIRST, CHAINLINKS_TOTALS, CHAINLINKS_RES, CHAINLINKS_LINKS,
     CHAINLINKS_KEPT, CHAINLINKS_SEQ_OFF, CHAINLINKS_SEQS,
+    // ---- pick_mappings_api.cpp (nothing stays): the reads, their offsets and generators; the chains and alignments with their offsets; the mappings and
+    // edit runs; an alignment's first mapping slot; a slot's from_length, an alignment's two sums, multiplicity and sort score; the results and verdicts;
+    // the picked alignments, scores and multiplicities on their way back; the pick's reads and its slab
+    PICK_READS, PICK_READ_OFF, PICK_RNG, PICK_CHAIN_OFF, PICK_CHAINS, PICK_ALN_OFF, PICK_ALNS, PICK_MAPPINGS, PICK_EDITS, PICK_SLOT_OFF, PICK_FROM_LEN, PICK_SUMS,
+    PICK_ALN_MULT, PICK_ALN_SORT, PICK_RES, PICK_VERDICTS, PICK_PICKED, PICK_SCORES, PICK_OUT_MULT, PICK_IDS, PICK_SLAB,
     // ---- gssw_wide_window_api.cpp (nothing stays): the call's problems, reads and verdicts; a sub-batch's windows, per-node temporaries, sizes, their
     // sums, the order's keys; the results and ops packed for the way back.  The arenas the wide kernels read are the WIDE_* buffers (aliases below)
     WIDEWIN_PROBLEMS, WIDEWIN_READS, WIDEWIN_META, WIDEWIN_SUB, WIDEWIN_STORE, WIDEWIN_NODE_FLAGS, WIDEWIN_SLOT_AT, WIDEWIN_PRED_AT, WIDEWIN_WIN_SLOTS,

@@ -1748,3 +1748,79 @@ int vgh_chain_links(const vgk_chain_links_scheme* scheme, uint32_t n_reads, cons
     } catch (std::exception& e) { g_last_error = e.what(); return -1; }
 }
 }  // extern "C"
+
+// ---- a long read's mappings (pick_mappings.hpp): the checker and CPU baseline of vgk_pick_mappings ---------------------------------------------------------
+#include "pick_mappings.hpp"
+extern "C" {
+// vgk_pick_mappings' arguments less the context, reads dealt over `threads` host threads; the same codes
+int vgh_pick_mappings(const vgk_pick_scheme* scheme, uint32_t n_reads, const char* reads, const uint64_t* read_off, uint32_t* rng_state, const uint64_t* chain_off,
+                      const vgk_pick_chain* chains, const uint64_t* aln_off, const vgk_pick_alignment* alns, const vgk_chain_mapping* mappings, size_t n_mappings,
+                      const uint32_t* edits, size_t n_edits, vgk_pick_result* results, vgk_pick_verdict* verdicts, uint32_t* picked, int32_t* scores, double* multiplicity,
+                      size_t cap, size_t* written, int threads) {
+    try {
+        if (written) *written = 0;
+        if (!scheme || (scheme->flags & ~(uint32_t)VGK_PICK_SORT_BY_CHAIN_SCORE) || scheme->max_multimaps == 0 || std::isnan(scheme->min_unique_node_fraction)) return VGK_EINVAL;
+        if (!n_reads) return VGK_OK;
+        if (rng_state && !reads) return VGK_EINVAL;
+        // the call: offsets ascend from 0
+        if (chain_off[0] != 0 || aln_off[0] != 0 || (rng_state && read_off[0] != 0)) return VGK_EINVAL;
+        for (uint32_t r = 0; r < n_reads; ++r) if (chain_off[r + 1] < chain_off[r] || aln_off[r + 1] < aln_off[r] || (rng_state && read_off[r + 1] < read_off[r])) return VGK_EINVAL;
+        const uint64_t room = aln_off[n_reads] + n_reads;
+        if (written) *written = (size_t)room;
+        if (room > cap) return VGK_EOPS;
+        PickScheme S; S.min_unique_node_fraction = scheme->min_unique_node_fraction; S.max_multimaps = scheme->max_multimaps; S.sort_by_chain_score = (scheme->flags & VGK_PICK_SORT_BY_CHAIN_SCORE) != 0;
+        std::fill(picked, picked + room, 0u); std::fill(scores, scores + room, 0); std::fill(multiplicity, multiplicity + room, 0.0);
+        over_reads(n_reads, threads, [&](uint32_t r) {
+            const uint64_t clo = chain_off[r], C = chain_off[r + 1] - clo, lo = aln_off[r], A = aln_off[r + 1] - lo;
+            vgk_pick_result R{};
+            for (uint64_t i = 0; i < A; ++i) verdicts[lo + i] = vgk_pick_verdict{};
+            bool ok = true;
+            std::vector<int> chain_score_estimates(C); std::vector<double> multiplicity_by_chain(C); std::vector<ChainRange> chain_ranges(C);
+            for (uint64_t c = 0; c < C; ++c) {
+                const vgk_pick_chain& ch = chains[clo + c];
+                ok = ok && std::isfinite(ch.multiplicity);
+                chain_score_estimates[c] = ch.score_estimate; multiplicity_by_chain[c] = ch.multiplicity;
+                ChainRange& g = chain_ranges[c];
+                g.component = ch.range.component; g.root_snarl = (ch.range.flags & VGK_CHAIN_RANGE_ROOT_SNARL) != 0; g.child_start = ch.range.child_start; g.child_end = ch.range.child_end;
+                g.offset_start = (size_t)ch.range.offset_start; g.offset_end = (size_t)ch.range.offset_end;
+            }
+            std::vector<PickAlignment> alignments(A); std::vector<size_t> alignments_to_source(A), chain_count_by_alignment(A);
+            for (uint64_t i = 0; i < A && ok; ++i) {
+                const vgk_pick_alignment& a = alns[lo + i];
+                if (a.source >= C || (uint64_t)a.result.mapping_begin + a.result.n_mappings > n_mappings) { ok = false; break; }
+                alignments_to_source[i] = a.source; chain_count_by_alignment[i] = (size_t)a.item_count; alignments[i].score = a.score;
+                for (uint32_t k = 0; k < a.result.n_mappings && ok; ++k) {
+                    const vgk_chain_mapping& m = mappings[a.result.mapping_begin + k];
+                    if ((uint64_t)m.edit_begin + m.n_edits > n_edits) { ok = false; break; }
+                    PickMapping pm; pm.has_position = m.node != VGK_WFA_NO_NODE; pm.node_id = m.node >> 1; pm.is_reverse = (m.node & 1u) != 0;
+                    for (uint32_t x = 0; x < m.n_edits; ++x) {
+                        const uint32_t e = edits[m.edit_begin + x], kind = e & 3u; const size_t len = e >> 2;
+                        PickEdit pe; pe.match = kind == VGK_WFA_MATCH; pe.from_length = kind == VGK_WFA_INSERTION ? 0 : len; pe.to_length = kind == VGK_WFA_DELETION ? 0 : len;
+                        pm.edits.push_back(pe);
+                    }
+                    alignments[i].path.push_back(std::move(pm));
+                }
+            }
+            if (!ok) { R.status = VGK_EINVAL; results[r] = R; return; }
+            const std::vector<double> multiplicity_by_alignment = fix_up_multiplicities(alignments_to_source, chain_score_estimates, chain_ranges, multiplicity_by_chain, chain_count_by_alignment);
+            FunnelRng g(reads, read_off, rng_state, r);
+            const PickedMappings p = pick_mappings_from_alignments(S, alignments, multiplicity_by_alignment, alignments_to_source, chain_score_estimates, g.rng.get());
+            g.keep(rng_state, r);
+            R.status = VGK_OK; R.first = (uint32_t)(lo + r); R.n_scores = (uint32_t)p.scores.size(); R.n_mappings = (uint32_t)p.n_mappings; R.unmapped = p.unmapped ? 1 : 0;
+            results[r] = R;
+            for (size_t k = 0; k < p.scores.size(); ++k) {
+                picked[R.first + k] = p.picked[k] == std::numeric_limits<size_t>::max() ? 0xffffffffu : (uint32_t)p.picked[k];
+                scores[R.first + k] = p.scores[k]; multiplicity[R.first + k] = p.multiplicity_by_mapping[k];
+            }
+            for (uint64_t i = 0; i < A; ++i) {
+                vgk_pick_verdict v{};
+                v.identity = p.identity[i]; v.fate = p.fate[i];
+                if (p.evaluated[i]) v.fraction_unique = p.fraction_unique[i];
+                else { const uint64_t bits = VGK_PICK_NOT_EVALUATED; std::memcpy(&v.fraction_unique, &bits, 8); }
+                verdicts[lo + i] = v;
+            }
+        });
+        return VGK_OK;
+    } catch (std::exception& e) { g_last_error = e.what(); return -1; }
+}
+}  // extern "C"

@@ -656,6 +656,74 @@ def chain_links(eng, scheme, reads, read_off, anchor_off, anchors, sites, items,
     return eng.chain_links(scheme, reads, read_off, anchor_off, anchors, sites, items, dist_off, dist, chains)[1]
 
 
+def pick_alignments(source, item_count, score, results):
+    """capi.PICK_ALIGNMENT_DT records from their columns: the chain each alignment came from (numbered within its read), the better_or_equal_count its chain's
+    walk passed in, its final score, and its vgk_chain_result (ChainStage.run(compose=True)["alignments"][0], or rows of it)"""
+    alns = np.zeros(len(source), dtype=capi.PICK_ALIGNMENT_DT)
+    alns["source"] = source; alns["item_count"] = item_count; alns["score"] = score; alns["result"] = np.asarray(results, dtype=capi.CHAIN_RESULT_DT)
+    return alns
+
+
+def pick_mappings(eng, scheme, reads, read_off, chain_off, chains, aln_off, alns, alignments, rng_state=None, threads=0):
+    """vgk_pick_mappings for a batch of long reads (include/vgk_engine.h): which of a read's chain alignments are its mappings, every counted score and its
+    multiplicity in the walk's order, the unmapped flag.  alignments: (results, mappings, runs) as ChainStage.run(compose=True) answers them — alns[].result
+    names mappings in it.  eng None: the host shim (vgh_pick_mappings, reads dealt over `threads` host threads) -> capi.pick_mappings_call's dict"""
+    _, mappings, runs = alignments
+    if eng is None:
+        rc, out = capi.pick_mappings_call(_host_lib().vgh_pick_mappings, (), scheme, reads, read_off, chain_off, chains, aln_off, alns, mappings, runs, rng_state=rng_state,
+                                          tail=(ctypes.c_int(threads),))
+        if rc:
+            raise RuntimeError("vgh_pick_mappings: %d" % rc)
+        return out
+    return eng.pick_mappings(scheme, reads, read_off, chain_off, chains, aln_off, alns, mappings, runs, rng_state=rng_state)[1]
+
+
+def long_read_mapq(eng, scheme, reads, read_off, chain_off, chains, aln_off, alns, alignments, log_base, k=0, explored=None, quality=None, score_scale=1.0, score_window=0,
+                   min_mapq0_score=0, rng_state=None, threads=0):
+    """How map_from_chains ends (src/minimizer_mapper_from_chains.cpp:960-1112): pick_mappings, then vgk_read_mapq in its first-score form
+    (VGK_READ_MAPQ_FIRST) over the pick's scores, multiplicities and unmapped flags with score_scale / score_window, then the demapping (:1070-1091): a read of
+    mapping quality 0 whose top score is below min_mapq0_score becomes one unmapped entry of score 0.  explored: dict(minimizer_off, minimizers, regions,
+    explored) for the explored cap, None: no cap (use_explored_cap == false).  eng None: the host shim for both steps.
+    -> dict(pick, per_read READ_MAPQ_RESULT_DT, read_mapq int32 per read, demapped bool per read, score_off / scores (after demapping), n_mappings per read,
+    mapq int32 per alignment as gaf_lines(mapq=...) takes it (the primary carries the read's, every other 0), reported / secondary bool per alignment)"""
+    n = len(chain_off) - 1
+    aln_off = np.ascontiguousarray(aln_off, dtype=np.uint64)
+    pick = pick_mappings(eng, scheme, reads, read_off, chain_off, chains, aln_off, alns, alignments, rng_state=rng_state, threads=threads)
+    res = pick["results"]
+    if (res["status"] != 0).any():
+        raise ValueError("long_read_mapq: read %d is malformed" % int(np.flatnonzero(res["status"] != 0)[0]))
+    counts = res["n_scores"].astype(np.int64); score_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+    at = np.repeat(res["first"].astype(np.int64) - score_off[:-1].astype(np.int64), counts) + np.arange(int(counts.sum()), dtype=np.int64)      # where each dense entry lies
+    scores = pick["scores"][at]; mult = pick["multiplicity"][at]; picked = pick["picked"][at]
+    unmapped = res["unmapped"].astype(np.uint8)
+    flags = capi.READ_MAPQ_FIRST | (capi.READ_MAPQ_NO_EXPLORED_CAP if explored is None else 0)
+    mq_scheme = capi.ReadMapqScheme(float(log_base), float(score_scale), int(score_window), int(k), int(flags), 0)
+    e = explored if explored is not None else dict(minimizer_off=np.zeros(n + 1, dtype=np.uint64), minimizers=np.zeros(0, dtype=capi.READ_MINIMIZER_DT),
+                                                   regions=np.zeros(0, dtype=capi.MINIMIZER_REGION_DT), explored=np.zeros(0, dtype=np.uint8))
+    if eng is None:
+        rc, per_read = capi.read_mapq_call(_host_lib().vgh_read_mapq, (), mq_scheme, score_off, scores, e["minimizer_off"], e["minimizers"], e["regions"], e["explored"], read_off,
+                                           quality, mult, unmapped, tail=(ctypes.c_int(threads),))
+        if rc:
+            raise RuntimeError("vgh_read_mapq: %d" % rc)
+    else:
+        per_read = eng.read_mapq(mq_scheme, score_off, scores, e["minimizer_off"], e["minimizers"], e["regions"], e["explored"], read_off, quality, mult, unmapped)
+    read_mapq = per_read["mapq"].astype(np.int32)
+    lo = score_off[:-1].astype(np.int64)
+    demapped = (read_mapq == 0) & (counts > 0) & (scores[np.minimum(lo, max(len(scores) - 1, 0))] < min_mapq0_score) if len(scores) else np.zeros(n, dtype=bool)
+    n_mappings = np.where(demapped, 1, res["n_mappings"].astype(np.int64) + res["unmapped"].astype(np.int64))      # (the unmapped entry is a mapping of its own)
+    keep = np.ones(len(scores), dtype=bool); rank = np.arange(len(scores), dtype=np.int64) - np.repeat(lo, counts)
+    keep[np.repeat(demapped, counts) & (rank > 0)] = False
+    scores = np.where(np.repeat(demapped, counts), 0, scores).astype(np.int32)[keep]
+    out_counts = np.where(demapped, 1, counts)
+    per_aln = np.zeros(len(alns), dtype=np.int32); reported = np.zeros(len(alns), dtype=bool); secondary = np.zeros(len(alns), dtype=bool)
+    is_mapping = (rank < np.repeat(res["n_mappings"].astype(np.int64), counts)) & ~np.repeat(demapped, counts) & (picked != capi.PICK_NONE)
+    which = np.repeat(aln_off[:-1].astype(np.int64), counts)[is_mapping] + picked[is_mapping].astype(np.int64)
+    reported[which] = True; secondary[which] = rank[is_mapping] > 0
+    per_aln[which] = np.where(rank[is_mapping] == 0, np.repeat(read_mapq, counts)[is_mapping], 0)
+    return dict(pick=pick, per_read=per_read, read_mapq=read_mapq, demapped=demapped, score_off=np.concatenate([[0], np.cumsum(out_counts)]).astype(np.uint64), scores=scores,
+                n_mappings=n_mappings, mapq=per_aln, reported=reported, secondary=secondary)
+
+
 def chains_to_stage_input(graph_of, out, chains, read_off, anchor_off, anchor_length, anchor_node_offset, anchor_path_off, anchor_nodes, route=True):
     """what ChainStage reads, from chain_links' answer `out`: one stage read per chain — its links as the table (mode, end points, bases, graph distance,
     where each starts in its read, that read's length), its kept anchors' anchor_length, anchor_node_offset, anchor_path_off and anchor_nodes gathered by
